@@ -12,8 +12,8 @@ One step = one 64-spp C2 frame rendered by the HIP megakernel, one process per G
   pixel id, path_tracer.cu:36-46/336-339, so the assembled frame is bit-identical to the 1-GPU frame)
   and every step ends with an RCCL gather over xGMI of the presented BGRA8 framebuffer to rank 0
   (--gather frame; the reference reads this buffer back every frame, path_tracer.cu:385) or of the
-  float accumulators (--gather accum). After the timed steps the float accumulators are gathered
-  once and checked.
+  float accumulators (--gather accum). With --full the float accumulators are gathered once after the
+  timed steps and the last gathered frame is checked.
 * N > 1, --scaling weak (opt-in): every rank renders the full frame with its own RNG streams (seed
   1984 + rank): N independent estimates, no collective in the timed region.
 
@@ -21,7 +21,15 @@ value = closest-hit queries traced by all ranks in the K timed steps / the max o
 barrier-bracketed wall time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--scaling strong|weak]
+    python bench.py --full ...            # + oracle check, roofline, CPU baseline (see below)
+    python bench.py --dump-outputs DIR    # + the last step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds everything else
+the benchmark measures or checks: the first frame against the CPU oracle (rmse_vs_oracle,
+bitexact_frac_vs_oracle), at N > 1 the gather check and the float accumulators gathered after timing, the
+certain / sky pixel counts, the roofline from the stored profiles, and the CPU baseline (cpu_baseline;
+--no-cpu-baseline leaves it out).
 
 Without torch.distributed.run, --gpus N > 1 starts its N rank processes itself (before anything
 touches the GPU) and returns rank 0's JSON line.
@@ -56,13 +64,24 @@ def parse():
                     help="untimed steps (default 10; 5 for the streamed configs c4 / c5, whose first 4 launches time "
                          "both camera-ray paths, DESIGN.md §3.5)")
     ap.add_argument("--config", default="c2")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the first frame checked against the CPU oracle, the gather "
+                         "check and the assembled float frame at N > 1, the certain / sky pixel counts, the roofline "
+                         "from the stored profiles and the CPU baseline (a plain run sets up, warms up, times the "
+                         "steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last step left with the caller as DIR/<name>.npy "
+                         "(float32 / float64): accum (the float4 accumulators), bgra (the presented BGRA8 frame), "
+                         "rays (closest-hit queries of the timed steps); a seeded sample of the pixels where a full "
+                         "array would pass the size cap")
     ap.add_argument("--spp", type=int, default=0,
                     help="samples per pixel per step (default: the config's; a progressive pass of C5's 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=60.0,
                     help="wall time of the CPU-baseline sample (a bounded sample: the default run stays within "
                          "minutes; BASELINE.md §3's 60-s runs: --cpu-seconds 60)")
-    ap.add_argument("--verify-rows", type=int, default=16)
+    ap.add_argument("--verify-rows", type=int, default=16,
+                    help="--full: rows of the first frame compared with the CPU oracle (0: no comparison)")
     ap.add_argument("--pmc-json", default="",
                     help="PMC traffic of the config's launch (tools/pmc_traffic.py; default: the newest "
                          "profiles/r0*/pmc_traffic_<config>*.json whose spp_per_launch equals this run's)")
@@ -456,6 +475,30 @@ def fma_flavour_rmse():
         return None
 
 
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 1984
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <dirname>/<name>.npy, float32 (float64 stays float64). The arrays share
+    DUMP_MAX_BYTES: an array whose rows pass its share is cut to a fixed sample of them (ascending row indices
+    drawn without replacement by numpy's default_rng(DUMP_SEED), so two runs keep the same rows)."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for k, a in arrays.items()}
+    even = DUMP_MAX_BYTES // len(arrays) - 4096                           # 4096: the .npy header
+    big = [k for k, a in arrays.items() if a.nbytes > even]
+    # the arrays past an even share divide what the others leave: equal shapes keep the same rows
+    share = (DUMP_MAX_BYTES - sum(a.nbytes + 4096 for k, a in arrays.items() if k not in big)) // max(1, len(big)) - 4096
+    for name, a in arrays.items():
+        if name in big and a.nbytes > share:
+            keep = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], share // a[0].nbytes, replace=False))
+            a = a[keep]
+        np.save(d / f"{name}.npy", a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -686,7 +729,7 @@ def main():
     first_lin = None
     for i in range(max(1, args.warmup)):
         step()
-        if i == 0 and args.verify_rows > 0:
+        if i == 0 and args.full and args.verify_rows > 0:
             first_lin = pt.read()[0]
     torch.cuda.synchronize()
     barrier()
@@ -719,13 +762,13 @@ def main():
     xcd_lists = bool(_o.value & (1 << 30))             # ... whose tiles were dealt to per-XCD lists
     if _o.value >= 0 and _o.value & (1 << 29):         # ... rendered by iqpt_anyhit_kernel instead (C4)
         launch_mode = "anyhit"
-    certain_px = certain_pixels(pt, _lib) if args.certain != "off" else 0
-    sky_px = sky_pixels(pt, _lib) if (args.certain != "off" and args.sky != "off") else 0
+    certain_px = certain_pixels(pt, _lib) if (args.full and args.certain != "off") else 0
+    sky_px = sky_pixels(pt, _lib) if (args.full and args.certain != "off" and args.sky != "off") else 0
 
     # the last step's gathered frame: rank 0's own rows of it must be its own frame (checks the gather path;
     # libiqpt's assembly puts them at rows 0, S, 2S, ... of the W x H frame, S = the split's ways)
     gather_check = None
-    if strong_multi and rank == 0 and assembled is not None:
+    if args.full and strong_multi and rank == 0 and assembled is not None:
         torch.cuda.synchronize()
         lin_own, bgra_own = pt.read()
         own = (lin_own.view(np.int32) if words == 4 else bgra_own.view(np.int32)).reshape(-1, cfg.width * words)
@@ -736,11 +779,12 @@ def main():
     # after timing: the float frame on rank 0 (strong: the gathered accumulators assembled, bit-identical to
     # one GPU's frame; weak: the N independent estimates averaged)
     frame = None
-    if world > 1 and lib_gather:
+    want_frame = world > 1 and bool(args.full or args.save_frame or args.dump_outputs)   # the same on every rank
+    if want_frame and lib_gather:
         acc = torch.zeros((cfg.width * cfg.height, 4), dtype=torch.float32, device="cuda") if rank == 0 else None
         pt.gather_accum(0, acc.data_ptr() if rank == 0 else 0, acc.numel() * 4 if rank == 0 else 0)
         frame = acc
-    elif world > 1:
+    elif want_frame:
         acc = torch.zeros((max_px, 4), dtype=torch.float32, device=tdev)
         fetch(acc, "accum")
         if weak:
@@ -841,43 +885,59 @@ def main():
             "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
             # the libiqpt that ran (its ABI; an A/B --lib may be an older build)
             "lib": {"path": str(_lib.LIB_PATH.name) if not args.lib else args.lib, "abi": _lib.LOADED_ABI},
-            **({"gather": "stream-ordered" if stream_gather else "blocking", "gather_check": gather_check}
-               if strong_multi else {}),
+            **({"gather": "stream-ordered" if stream_gather else "blocking"} if strong_multi else {}),
             "msamples_per_s": round(samples / elapsed / 1e6, 3),
             "rays_per_sample": round(total_rays / samples, 5),
-            # value counts the closest-hit queries the reference performs for the same image; the camera rays
-            # of certain pixels are among them but resolved by one interval proof per pixel
-            # (every ray of the pixel's jitter square hits an emissive triangle first) instead of per-ray tests
-            "certain_pixels": {"pixels": certain_px, "frac_of_owned_pixels": round(certain_px / max(1, npix_owned), 5),
-                               "frac_of_rays_counted": round(certain_px * spp_step * args.steps / max(1.0, float(rays)), 5),
-                               "note": "rank 0's pixels whose camera rays are proven (iq_interval.h tri_certain) to end "
-                                       "on an emissive triangle: their samples take the two camera draws and fold "
-                                       "the clamped (1, 1, 1) without a per-ray intersection test; bit-identical "
-                                       "results (tests/test_gpu_certain.py)"},
-            # pixels proven (iq_interval.h) to miss every primitive: their samples are one camera ray each, the sky
-            # gradient, rendered by iqpt_sky_kernel without an intersection test
-            "sky_pixels": {"pixels": sky_px, "frac_of_owned_pixels": round(sky_px / max(1, npix_owned), 5),
-                           "frac_of_rays_counted": round(sky_px * spp_step * args.steps / max(1.0, float(rays)), 5)},
-            "rmse_vs_oracle": rmse_v,
-            "bitexact_frac_vs_oracle": bitexact,
             "setup_ms": {k: round(v, 2) for k, v in setup.items()},
-            "parity_basis": ("bit-exact vs the CPU oracle (oracle/iqpt_oracle.c: the reference restated with "
-                             "FMA contraction off and shared iq_fp.h transcendentals); unpinned vs the nvcc/cuRAND "
-                             "reference binary, which cannot be built here"),
-            "fma_flavour_rmse_c2": fma_flavour_rmse(),
-            "roofline": roofline(cfg, args, world, rays_per_launch, kern_avg_ms, launch_mode, part_world, spp_step,
-                                 npix_owned, (certain_px + sky_px) * spp_step * args.steps / max(1.0, float(rays))),
         }
         if strong_multi or world > 1:
             out["per_rank"] = per_rank
-        out["roofline"]["launch_duration_ms"] = round(kern_ms / max(1, launches), 4)
-        out["roofline"]["overlapped_launches"] = bool(kern_span_ms < 0.98 * kern_ms)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, pk, cam, args.cpu_seconds)
+        if args.full:
+            out.update({
+                # value counts the closest-hit queries the reference performs for the same image; the camera rays
+                # of certain pixels are among them but resolved by one interval proof per pixel
+                # (every ray of the pixel's jitter square hits an emissive triangle first) instead of per-ray tests
+                "certain_pixels": {"pixels": certain_px, "frac_of_owned_pixels": round(certain_px / max(1, npix_owned), 5),
+                                   "frac_of_rays_counted": round(certain_px * spp_step * args.steps / max(1.0, float(rays)), 5),
+                                   "note": "rank 0's pixels whose camera rays are proven (iq_interval.h tri_certain) to end "
+                                           "on an emissive triangle: their samples take the two camera draws and fold "
+                                           "the clamped (1, 1, 1) without a per-ray intersection test; bit-identical "
+                                           "results (tests/test_gpu_certain.py)"},
+                # pixels proven (iq_interval.h) to miss every primitive: their samples are one camera ray each, the sky
+                # gradient, rendered by iqpt_sky_kernel without an intersection test
+                "sky_pixels": {"pixels": sky_px, "frac_of_owned_pixels": round(sky_px / max(1, npix_owned), 5),
+                               "frac_of_rays_counted": round(sky_px * spp_step * args.steps / max(1.0, float(rays)), 5)},
+                "rmse_vs_oracle": rmse_v,
+                "bitexact_frac_vs_oracle": bitexact,
+                "parity_basis": ("bit-exact vs the CPU oracle (oracle/iqpt_oracle.c: the reference restated with "
+                                 "FMA contraction off and shared iq_fp.h transcendentals); unpinned vs the nvcc/cuRAND "
+                                 "reference binary, which cannot be built here"),
+                "fma_flavour_rmse_c2": fma_flavour_rmse(),
+                "roofline": roofline(cfg, args, world, rays_per_launch, kern_avg_ms, launch_mode, part_world, spp_step,
+                                     npix_owned, (certain_px + sky_px) * spp_step * args.steps / max(1.0, float(rays))),
+            })
+            if strong_multi:
+                out["gather_check"] = gather_check
+            out["roofline"]["launch_duration_ms"] = round(kern_ms / max(1, launches), 4)
+            out["roofline"]["overlapped_launches"] = bool(kern_span_ms < 0.98 * kern_ms)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg, pk, cam, args.cpu_seconds)
         if args.save_frame:
             if frame is None:
                 frame = torch.from_numpy(pt.read()[0])
             np.save(args.save_frame, frame.cpu().numpy())
+        if args.dump_outputs:
+            # what the last timed step left with the caller: the float accumulators and the presented BGRA8
+            # frame (N > 1: what rank 0 assembled; --gather accum gathers no BGRA8 frame, bgra is then rank 0's
+            # own rows), and the closest-hit queries of the timed steps
+            lin_own, bgra_own = pt.read()
+            accum = frame.cpu().numpy() if frame is not None else lin_own
+            if strong_multi and words == 1 and assembled is not None:
+                bgra = assembled.reshape(-1).cpu().numpy().view(np.uint8).reshape(-1, 4)
+            else:
+                bgra = bgra_own
+            dump_outputs(args.dump_outputs, {"accum": accum.reshape(-1, 4), "bgra": bgra.reshape(-1, 4),
+                                             "rays": np.array([total_rays], dtype=np.float64)})
         print(json.dumps(out), flush=True)
     pt.close()
     if use_pg:

@@ -63,6 +63,21 @@ def main():
             lib.iqo_rng_init(w, C.byref(ps), 1984, st.ctypes.data_as(C.POINTER(C.c_uint32)))
             kat.append([w, h, pid, *st[0].tolist()])
     np.savez_compressed(HERE / "rng_kat.npz", kat=np.array(kat, dtype=np.uint64))
+    rocrand_jump_tables()
+
+
+def rocrand_jump_tables():
+    """rocRAND's own XORWOW sequence-jump matrices (A^(4^i * 2^67), rocrand_xorwow_precomputed.h of a ROCm
+    install): the independent tables tests/test_xorwow.py pins iq_xorwow.h's jumps against."""
+    import os
+    import re
+    header = Path(os.environ.get("ROCM_PATH", "/opt/rocm")) / "include/rocrand/rocrand_xorwow_precomputed.h"
+    m = re.search(r"h_xorwow_sequence_jump_matrices\[XORWOW_JUMP_MATRICES\]\[XORWOW_SIZE\]\s*=\s*\{(.*?)\};",
+                  header.read_text(), re.S)
+    nums = [int(x, 0) for x in re.findall(r"0x[0-9a-fA-F]+|\d+", m.group(1).replace("U", ""))]
+    roc = np.array(nums, dtype=np.uint64).astype(np.uint32).reshape(-1, 800)
+    np.savez_compressed(HERE / "rocrand_xorwow_jump.npz", sequence_jump=roc[:4])
+    print("rocrand_xorwow_jump", roc.shape)
 
 
 if __name__ == "__main__":

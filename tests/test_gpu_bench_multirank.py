@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 def _bench(tmp_path, gpus, name, extra=(), timeout=240):
     out = tmp_path / f"{name}.npy"
     cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--verify-rows", "2", "--save-frame", str(out), *extra]
+           "--full", "--no-cpu-baseline", "--verify-rows", "2", "--save-frame", str(out), *extra]
     if gpus > 1:
         cmd += ["--backend", "gloo", "--one-device"]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=REPO)

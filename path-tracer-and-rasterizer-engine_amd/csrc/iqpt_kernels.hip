@@ -1367,6 +1367,8 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
     // ---- stats (kOptStats): wave-level counters
     unsigned long long s_iter = 0, s_ready = 0, s_scatter_exec = 0, s_scatter_lanes = 0, s_term_exec = 0,
                        s_term_lanes = 0;
+    // kOptPipe: iterations whose one scatter served both ray a's sphere hits and promoted ray b's
+    unsigned long long s_scatter_both = 0;
     unsigned long long s_tests[2] = {0, 0};   // wave-level triangle / sphere pair tests (culled resident path)
     unsigned long long s_full = 0;            // iterations forced to the full loop (a secondary ray in the wave)
     unsigned long long s_refill = 0, s_refill_lanes = 0;   // refills that started pixels, pixels started
@@ -1735,92 +1737,134 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
             }
             phase(0);
             wave_rays += (uint64_t)__popcll(__ballot(active));
-            // at most two shading rounds: ray a's hit, then (ray a ended the path) ray b's
-            bool pend = active, need_a = false;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                bool term = false;
-                uint32_t md_end = 0;
-                float Lx = 0.0f, Ly = 0.0f, Lz = 0.0f;
-                if (pend) {
-                    if (kind == kHitSphere) {
-                        if (OPT & kOptStats) ++s_scatter_lanes;
-                        const float* q = reinterpret_cast<const float*>(lds_sph + (size_t)(hidx >> 1) * kSphPairFloat4) +
-                                         (hidx & 1u);
-                        const float s = oren_nayar_scatter<OPT>(make_float4(q[0], q[2], q[4], q[6]), closest, ray, st);
-                        if (depth + 1 >= p.max_depth) {
-                            term = true;             // the last record is this scatter (biased, :252)
-                            md_end = 1;
-                            Lx = s;
-                            Ly = s;
-                            Lz = s;
-                        } else {
-                            lds_stk[(uint32_t)depth * kRenderBlock + threadIdx.x] = s;
-                            ++depth;
-                        }
-                    } else if (kind == kHitTri) {
-                        term = true;                 // emissive(1, 10): att 10, cos = pdf = 1
-                        Lx = 10.0f;
-                        Ly = 10.0f;
-                        Lz = 10.0f;
-                    } else {
-                        term = true;                 // sky gradient, :308-313
-                        const float a = (ray.dy + 1.0f) * 0.5f;
-                        const float one_a = 1.0f - a;
-                        Lx = one_a + a * 0.5f;
-                        Ly = one_a + a * 0.7f;
-                        Lz = one_a + a * 1.0f;
-                    }
+            // Three shading stages in wave order: ray a's terminal hits fold (and take ray b where the path ended
+            // without drawing), then ONE scatter serves ray a's sphere hits and the promoted ray b's together (no
+            // lane scatters twice in an iteration: a scatter of ray a keeps ray a, ray b is served only after ray a
+            // ended), then the promoted rays' terminal hits and the scatters that reached max_depth fold. Each
+            // lane's own operations keep the order of the reference.
+            bool need_a = false;
+            // the sky gradient of a miss, :308-313
+            auto sky = [&](float& Lx, float& Ly, float& Lz) {
+                const float a = (ray.dy + 1.0f) * 0.5f;
+                const float one_a = 1.0f - a;
+                Lx = one_a + a * 0.5f;
+                Ly = one_a + a * 0.7f;
+                Lz = one_a + a * 1.0f;
+            };
+            // a path's end: backward product (:321-324), clamp (:345-347), path_color = 0 + color, running mean
+            // (:356-358). True when the pixel's samples of this launch are done.
+            auto fold = [&](float Lx, float Ly, float Lz) -> bool {
+                float cx = Lx, cy = Ly, cz = Lz;
+                for (int i = depth - 1; i >= 0; --i) {
+                    const float f = lds_stk[(uint32_t)i * kRenderBlock + threadIdx.x];
+                    cx = cx * f;
+                    cy = cy * f;
+                    cz = cz * f;
                 }
+                cx = cx > 1.0f ? 1.0f : (cx < 0.0f ? 0.0f : cx);
+                cy = cy > 1.0f ? 1.0f : (cy < 0.0f ? 0.0f : cy);
+                cz = cz > 1.0f ? 1.0f : (cz < 0.0f ? 0.0f : cz);
+                const float2 tv = lds_tab[done];
+                float qx, qy, qz;
+                mean_terms<OPT>(0.0f + cx, 0.0f + cy, 0.0f + cz, lds_tab_n[done], tv.x, p.mean_tiny, qx, qy, qz);
+                acc.x = qx + acc.x * tv.y;
+                acc.y = qy + acc.y * tv.y;
+                acc.z = qz + acc.z * tv.y;
+                ++done;
+                depth = 0;
+                return done == p.spp;
+            };
+            auto count_terms = [&](bool term) {
                 if (OPT & kOptStats) {
-                    if (__ballot(pend && kind == kHitSphere)) ++s_scatter_exec;
                     const uint64_t tm = __ballot(term);
                     if (tm) {
                         ++s_term_exec;
                         s_term_lanes += (unsigned long long)__popcll(tm);
                     }
                 }
-                bool next = false;
-                if (term) {
-                    // backward product (:321-324), clamp (:345-347), path_color = 0 + color, running mean (:356-358)
-                    float cx = Lx, cy = Ly, cz = Lz;
-                    for (int i = depth - 1; i >= 0; --i) {
-                        const float f = lds_stk[(uint32_t)i * kRenderBlock + threadIdx.x];
-                        cx = cx * f;
-                        cy = cy * f;
-                        cz = cz * f;
-                    }
-                    cx = cx > 1.0f ? 1.0f : (cx < 0.0f ? 0.0f : cx);
-                    cy = cy > 1.0f ? 1.0f : (cy < 0.0f ? 0.0f : cy);
-                    cz = cz > 1.0f ? 1.0f : (cz < 0.0f ? 0.0f : cz);
-                    const float2 tv = lds_tab[done];
-                    float qx, qy, qz;
-                    mean_terms<OPT>(0.0f + cx, 0.0f + cy, 0.0f + cz, lds_tab_n[done], tv.x, p.mean_tiny, qx, qy, qz);
-                    acc.x = qx + acc.x * tv.y;
-                    acc.y = qy + acc.y * tv.y;
-                    acc.z = qz + acc.z * tv.y;
-                    ++done;
-                    depth = 0;
-                    if (done == p.spp) {
-                        store_pixel();
-                        if (kOverlap) finished = true;
-                        active = false;
-                    } else if (r == 0 && md_end == 0u && has_b) {
-                        // the path ended without drawing: ray b is the next sample's camera ray, its query done
-                        (void)xorwow_next(st);
-                        (void)xorwow_next(st);
-                        ray = ray_b;
-                        closest = cb;
-                        kind = kb;
-                        hidx = ib;
-                        next = true;
-                    } else {
-                        need_a = true;
-                    }
+            };
+            // ---- stage 1: ray a ended the path on an emissive triangle (emissive(1, 10): att 10, cos = pdf = 1) or
+            // the sky (ray a's own dy: read before ray b takes its place)
+            bool next = false;
+#if defined(IQPT_ONE_STORE)
+            bool stored = false;
+#endif
+            const bool term_a = active && kind != kHitSphere;
+            count_terms(term_a);
+            if (term_a) {
+                float Lx = 10.0f, Ly = 10.0f, Lz = 10.0f;
+                if (kind != kHitTri) sky(Lx, Ly, Lz);
+                if (fold(Lx, Ly, Lz)) {
+#if defined(IQPT_ONE_STORE)
+                    stored = true;
+#else
+                    store_pixel();
+                    if (kOverlap) finished = true;
+#endif
+                    active = false;
+                } else if (has_b) {
+                    // the path ended without drawing: ray b is the next sample's camera ray, its query done
+                    (void)xorwow_next(st);
+                    (void)xorwow_next(st);
+                    ray = ray_b;
+                    closest = cb;
+                    kind = kb;
+                    hidx = ib;
+                    next = true;
+                } else {
+                    need_a = true;
                 }
-                if (r == 0) wave_rays += (uint64_t)__popcll(__ballot(next));
-                pend = next;
             }
+            wave_rays += (uint64_t)__popcll(__ballot(next));
+            // ---- stage 2: the one scatter, for ray a's sphere hits and the promoted ray b's sphere hits
+            const bool scat = active && kind == kHitSphere;
+            bool md_end = false;
+            float sL = 0.0f;
+            if (OPT & kOptStats) {
+                const uint64_t sm = __ballot(scat), pm = __ballot(next);
+                if (sm) ++s_scatter_exec;
+                if ((sm & pm) && (sm & ~pm)) ++s_scatter_both;
+            }
+            if (scat) {
+                if (OPT & kOptStats) ++s_scatter_lanes;
+                const float* q = reinterpret_cast<const float*>(lds_sph + (size_t)(hidx >> 1) * kSphPairFloat4) +
+                                 (hidx & 1u);
+                sL = oren_nayar_scatter<OPT>(make_float4(q[0], q[2], q[4], q[6]), closest, ray, st);
+                if (depth + 1 >= p.max_depth) {
+                    md_end = true;                   // the last record is this scatter (biased, :252)
+                } else {
+                    lds_stk[(uint32_t)depth * kRenderBlock + threadIdx.x] = sL;
+                    ++depth;
+                }
+            }
+            // ---- stage 3: the promoted ray b's terminal hits and the scatters that reached max_depth (they drew:
+            // no second promotion)
+            const bool term_b = md_end || (next && kind != kHitSphere);
+            count_terms(term_b);
+            if (term_b) {
+                float Lx = sL, Ly = sL, Lz = sL;
+                if (!md_end) {
+                    Lx = Ly = Lz = 10.0f;
+                    if (kind != kHitTri) sky(Lx, Ly, Lz);
+                }
+                if (fold(Lx, Ly, Lz)) {
+#if defined(IQPT_ONE_STORE)
+                    stored = true;
+#else
+                    store_pixel();
+                    if (kOverlap) finished = true;
+#endif
+                    active = false;
+                } else {
+                    need_a = true;
+                }
+            }
+#if defined(IQPT_ONE_STORE)
+            if (stored) {
+                store_pixel();
+                if (kOverlap) finished = true;
+            }
+#endif
             phase(1);
             // the next iteration's rays: a new path's camera ray where a path ended without taking ray b, and the
             // camera ray of the sample after the current one (ray b is stale after any scatter or path end)
@@ -2421,6 +2465,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
             atomicAdd(p.stats + 10, s_full);
             atomicAdd(p.stats + 12, s_refill);
             atomicAdd(p.stats + 13, s_refill_lanes);
+            atomicAdd(p.stats + 22, s_scatter_both);
         }
         {
             // BVH work and the primitive tests executed, summed over the wave's lanes

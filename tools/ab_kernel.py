@@ -173,6 +173,8 @@ def main():
         tri_rays, tri_nodes, tri_pairs, sph_rays, sph_nodes, sph_tests = list(s)[14:20]
         stats = {"opt": stats_opt, "waves": waves, "iterations": it, "ready_lane_frac": ready / max(1, it * 64),
                  "active_lane_frac": active / max(1, it * 64), "scatter_exec_per_iter": sc_ex / max(1, it),
+                 # two-ray kernel: iterations whose scatter served ray a's hits and promoted ray b's together
+                 "scatter_both_per_iter": s[22] / max(1, it),
                  "scatter_lanes_per_exec": sc_l / max(1, sc_ex), "term_exec_per_iter": t_ex / max(1, it),
                  "term_lanes_per_exec": t_l / max(1, t_ex), "rays": pt.rays(),
                  "tri_pair_tests_per_iter": tri_tests / max(1, it), "sph_pair_tests_per_iter": sph_tests / max(1, it),

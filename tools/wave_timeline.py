@@ -4,7 +4,7 @@ option set (one ray or two rays per lane, kOptPipe), every wave's start / end (s
 iterations, and the launch's counters: iterations, active lanes per iteration (exec population), iterations that
 ran an Oren-Nayar scatter or a path end, iterations forced onto every pair by a secondary ray.
 
-    wave_timeline.py [--two-ray 1] [--overlap 1] [--crop x0,x1,y0,rows] [--out f.json]
+    wave_timeline.py [--two-ray 1] [--overlap 1] [--crop x0,x1,y0,rows] [--lib libiqpt_stats.so] [--out f.json]
 
 Waves are sorted by iteration count; the longest ones are the sphere tiles' chains that set the launch. With
 --overlap 1 two launches run at once (the production form); the timeline is the last launch's."""
@@ -32,9 +32,10 @@ ap.add_argument("--overlap", type=int, default=1)
 ap.add_argument("--crop", default="", help="x0,x1,y0,rows: a pixel set instead of the full frame")
 ap.add_argument("--warm", type=int, default=3)
 ap.add_argument("--out", default="")
+ap.add_argument("--lib", default="", help="load this prebuilt instrumented library (A/B against another tree's build)")
 args = ap.parse_args()
 
-_lib.LIB_PATH = _build.build_lib(stats=True)
+_lib.LIB_PATH = Path(args.lib).resolve() if args.lib else _build.build_lib(stats=True)
 lb = _lib.load()
 lb.iqpt_debug_set_kernel_options.argtypes = [C.c_void_p, C.c_int]
 lb.iqpt_debug_default_options.restype = C.c_int
@@ -106,7 +107,9 @@ res = {"config": args.config, "spp": spp, "two_ray": args.two_ray, "overlap": ar
        "kernel_ms": round(t / max(k, 1), 4), "waves": int(busy.sum()),
        "launch_iterations": v[0], "active_lanes_per_iteration": round(v[1] / max(v[0], 1), 2),
        "exec_population": round(v[1] / max(v[0], 1) / 64.0, 3),
-       "scatter_iteration_frac": round(v[3] / max(v[0], 1), 3), "scatter_lanes_per_scatter_iteration": round(v[4] / max(v[3], 1), 2),
+       "scatter_iteration_frac": round(v[3] / max(v[0], 1), 3),
+       # two-ray kernel: iterations whose one scatter served ray a's sphere hits and promoted ray b's together
+       "scatter_both_iteration_frac": round(v[22] / max(v[0], 1), 3), "scatter_lanes_per_scatter_iteration": round(v[4] / max(v[3], 1), 2),
        "end_iteration_frac": round(v[5] / max(v[0], 1), 3), "end_lanes_per_end_iteration": round(v[6] / max(v[5], 1), 2),
        "full_loop_iteration_frac": round(v[10] / max(v[0], 1), 3),
        "iters_per_wave": pct(iters[busy]), "wave_us": pct(dur[busy]), "us_per_iter": pct(us_iter),

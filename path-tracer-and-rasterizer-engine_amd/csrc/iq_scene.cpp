@@ -14,6 +14,7 @@
 #include "iq_host_math.hpp"
 #include "iqpt.h"
 #include "iqpt_internal.hpp"
+#include "raster/iqpt_raster.h"
 
 namespace {
 
@@ -354,6 +355,34 @@ int iqpt_scene_build_packet(iqpt_scene* s, iqpt_packet_desc* out) {            /
     out->num_materials = with_table ? (uint32_t)s->pk_mats.size() : 0u;
     out->tri_dc_material = with_table && !s->pk_tri_mat.empty() ? s->pk_tri_mat.data() : nullptr;
     out->sphere_dc_material = with_table && !s->pk_sph_mat.empty() ? s->pk_sph_mat.data() : nullptr;
+    return IQPT_OK;
+}
+
+int iqpt_scene_draw_list(const iqpt_scene* s, iqpt_draw_item* items, uint32_t capacity, uint32_t* count) {
+    if (!s || !count) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    // the walk of build_packet (scene.h:58-67), with both mesh types: rasterizer::draw_scene draws every model
+    std::vector<const model*> sorted;
+    for (const auto& kv : s->models) sorted.push_back(&kv.second);
+    std::sort(sorted.begin(), sorted.end(), [](const model* a, const model* b) {
+        if (a->mesh_name != b->mesh_name) return a->mesh_name < b->mesh_name;
+        return a->order < b->order;
+    });
+    *count = (uint32_t)sorted.size();
+    if (!items) return IQPT_OK;
+    for (uint32_t i = 0; i < *count && i < capacity; ++i) {
+        const model* pm = sorted[i];
+        const mesh& m = s->meshes.at(pm->mesh_name);
+        iqpt_draw_item& it = items[i];
+        std::memcpy(it.transform, pm->transform.m, sizeof it.transform);
+        it.vertices = m.vertices.empty() ? nullptr : m.vertices.data();
+        it.indices = m.indices.empty() ? nullptr : m.indices.data();
+        it.num_vertices = (uint32_t)m.vertices.size();
+        it.num_indices = (uint32_t)m.indices.size();
+        it.albedo[0] = 1.0f; it.albedo[1] = 0.0f; it.albedo[2] = 0.0f;      // pixel_shader.hlsl: albedo
+        if (pm->material >= 0)
+            for (int k = 0; k < 3; ++k) it.albedo[k] = s->materials[(size_t)pm->material].albedo[k];
+        it.mesh_type = m.type;
+    }
     return IQPT_OK;
 }
 

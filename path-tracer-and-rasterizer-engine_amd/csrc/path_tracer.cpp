@@ -40,10 +40,12 @@ void scene::add_model(const std::string& name, const std::string& mesh_name, con
                       const float rotation[4], const float translation[4]) {
     IQPT_THROW_FAILED(iqpt_scene_add_model(m_scene, name.c_str(), mesh_name.c_str(), scale, rotation, translation));
     m_modified = true;                                                     // scene.cu:49
+    m_revision += 1;
 }
 void scene::add_preset(const std::string& preset) {
     IQPT_THROW_FAILED(iqpt_scene_add_preset(m_scene, preset.c_str()));
     m_modified = true;
+    m_revision += 1;
 }
 iqpt_packet_desc scene::build_packet() const {
     iqpt_packet_desc pk{};

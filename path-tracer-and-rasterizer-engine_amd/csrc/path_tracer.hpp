@@ -35,8 +35,24 @@ private:
         if (st_ != IQPT_OK) throw ::iqpt::iqpt_exception(__LINE__, __FILE__, st_, iqpt_last_error()); \
     } while (0)
 
-// The rasterizer's shader objects are accepted and ignored, as by the reference path tracer.
-class shader {};
+// The rasterizer's shader object (shader.h): the path tracer accepts and ignores it, as the reference's does;
+// the rasterizer (raster/rasterizer.hpp) draws with shaders[0]'s view and projection once they were set.
+class shader {
+public:
+    // shader.cu:55-60: the view and projection of the frames drawn from now on (row-vector, m[r][c] row-major)
+    void update_view_proj(const float view[16], const float proj[16]);
+    // shader.cu:48-53: the model transform and its normal matrix inverse(store3x3(tr)) transposed
+    void update_transform(const float tr[16]);
+    bool has_view_proj() const { return m_has_view_proj; }
+    const float* view() const { return m_view; }
+    const float* projection() const { return m_proj; }
+    const float* model() const { return m_model; }
+    const float* normal_mat() const { return m_normal; }       // 3 rows of 4 floats
+
+private:
+    float m_view[16] = {}, m_proj[16] = {}, m_model[16] = {}, m_normal[12] = {};
+    bool m_has_view_proj = false;
+};
 
 // camera (camera.h:8-34): host-side constructor + the matrices the kernel consumes.
 class camera {
@@ -71,10 +87,16 @@ public:
     bool modified() const { return m_modified; }
     // scene::build_packet (scene.cu:104-181) — host arrays; the upload is iqpt_upload_packet.
     iqpt_packet_desc build_packet() const;
+    // the scene builder behind the facade (iqpt_raster_upload_scene takes it)
+    const iqpt_scene* handle() const { return m_scene; }
+    // counts the modifications: an engine that reads handle() keeps its own copy current without clearing
+    // modified(), which the path tracer's build_packet consumes (scene.cu:112)
+    uint64_t revision() const { return m_revision; }
 
 private:
     iqpt_scene* m_scene = nullptr;
     mutable bool m_modified = true;
+    uint64_t m_revision = 0;
 };
 
 class renderer_template {                                                  // renderer_template.h:6-12

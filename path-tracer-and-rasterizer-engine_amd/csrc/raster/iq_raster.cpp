@@ -1,0 +1,438 @@
+// iq_raster.cpp — the iqpt_raster_* C ABI (include/raster/iqpt_raster.h): device buffers, scene upload and
+// the draw sequence vertex -> setup -> (counter readback) -> bin -> sort -> tiles on the rasterizer's own
+// stream. The kernels are iq_raster_kernels.hip; the pipeline is DESIGN.md §9.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "iq_host_math.hpp"
+#include "iqpt_internal.hpp"
+#include "raster/iq_raster.hpp"
+#include "raster/iqpt_raster.h"
+
+namespace {
+
+int hip_fail(hipError_t e, const char* what) {
+    return iqpt::fail(IQPT_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
+}
+
+#define IQR_HIP(call)                                        \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return hip_fail(e_, #call);    \
+    } while (0)
+
+// a device buffer that only grows
+struct dbuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipError_t reserve(size_t want) {
+        if (want <= bytes) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) bytes = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// what a draw consumes: draws, their prefix ends, the index pool and the transformed vertices
+struct geometry {
+    dbuf draws, vend, tend, indices, mesh_verts, clip, wn;
+    uint32_t ndraws = 0, nverts = 0, ntris = 0;
+    bool transformed = false;     // clip / wn hold the current camera's vertices
+    void release() {
+        for (dbuf* b : {&draws, &vend, &tend, &indices, &mesh_verts, &clip, &wn}) b->release();
+    }
+};
+
+constexpr int kEvents = 6;
+
+}  // namespace
+
+struct iqpt_raster {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    iqr::frame_params fp{};
+    bool have_camera = false, have_scene = false, have_frame = false;
+    dbuf camera;                  // view[16], projection[16]
+    geometry scene, direct;       // the uploaded scene; the vertices of the last draw_clip
+    dbuf recs, cnt, frame, depth_samples, prim_samples, sort_temp;
+    dbuf keys[2], vals[2], ranges;
+    iqr::counters* host_cnt = nullptr;    // pinned
+    uint32_t last_nrec = 0, last_npairs = 0, last_ntris = 0;
+    hipEvent_t ev[kEvents] = {};
+    bool pending = false;         // the events of the last draw have not been added up yet
+    double total_ms = 0.0, stage_ms[5] = {};
+    uint64_t draws = 0;
+};
+
+namespace {
+
+int set_device(iqpt_raster* r) {
+    IQR_HIP(hipSetDevice(r->device));
+    return IQPT_OK;
+}
+
+int collect(iqpt_raster* r) {
+    if (!r->pending) return IQPT_OK;
+    IQR_HIP(hipEventSynchronize(r->ev[kEvents - 1]));
+    float ms = 0.0f;
+    for (int k = 0; k < 5; ++k) {
+        IQR_HIP(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
+        r->stage_ms[k] += ms;
+    }
+    IQR_HIP(hipEventElapsedTime(&ms, r->ev[0], r->ev[kEvents - 1]));
+    r->total_ms += ms;
+    r->draws += 1;
+    r->pending = false;
+    return IQPT_OK;
+}
+
+int upload(dbuf& b, const void* src, size_t bytes, hipStream_t s) {
+    IQR_HIP(b.reserve(std::max<size_t>(bytes, 16)));
+    if (bytes) IQR_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    return IQPT_OK;
+}
+
+int run_draw(iqpt_raster* r, geometry& g, bool vertex_stage) {
+    if (int st = set_device(r)) return st;
+    if (int st = collect(r)) return st;
+    hipStream_t s = r->stream;
+    const iqr::frame_params& fp = r->fp;
+    IQR_HIP(hipEventRecord(r->ev[0], s));
+    if (vertex_stage && !g.transformed) {
+        IQR_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
+                                   g.mesh_verts.as<float>(), r->camera.as<float>(), r->camera.as<float>() + 16,
+                                   g.clip.as<float>(), g.wn.as<float>()));
+        g.transformed = true;
+    }
+    IQR_HIP(hipEventRecord(r->ev[1], s));
+
+    // setup: records and pair positions are claimed with two counters; a record buffer that proves too small
+    // is grown to the count the pass reported and the pass is redone (never a silent limit)
+    uint32_t nrec = 0, npairs = 0;
+    if (g.ntris) {
+        size_t cap = std::max<size_t>(r->recs.bytes / sizeof(iqr::setup_rec), 1024);
+        for (int attempt = 0;; ++attempt) {
+            IQR_HIP(r->recs.reserve(cap * sizeof(iqr::setup_rec)));
+            IQR_HIP(hipMemsetAsync(r->cnt.p, 0, sizeof(iqr::counters), s));
+            IQR_HIP(iqr::launch_setup(s, fp, g.draws.as<iqr::draw_rec>(), g.ndraws, g.tend.as<uint32_t>(), g.ntris,
+                                      g.indices.as<uint32_t>(), g.clip.as<float>(), g.wn.as<float>(),
+                                      r->recs.as<iqr::setup_rec>(), (uint32_t)std::min<size_t>(cap, 0xffffffffu),
+                                      r->cnt.as<iqr::counters>()));
+            IQR_HIP(hipMemcpyAsync(r->host_cnt, r->cnt.p, sizeof(iqr::counters), hipMemcpyDeviceToHost, s));
+            IQR_HIP(hipStreamSynchronize(s));
+            if (r->host_cnt->npairs >= 0xffffffffull || r->host_cnt->nrec >= 0xffffffffull)
+                return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^32 (tile, triangle) pairs in one frame");
+            if (r->host_cnt->nrec <= cap) break;
+            if (attempt) return iqpt::fail(IQPT_ERR_HIP, "setup record count changed between passes");
+            cap = (size_t)r->host_cnt->nrec;
+        }
+        nrec = (uint32_t)r->host_cnt->nrec;
+        npairs = (uint32_t)r->host_cnt->npairs;
+    }
+    IQR_HIP(hipEventRecord(r->ev[2], s));
+
+    const int in = 0, out = 1;
+    // sort key: tile << key_bits | (submission index << 3 | piece), key_bits just wide enough for this draw
+    unsigned key_bits = iqr::kPieceBits + 1;
+    while ((1ull << key_bits) < ((unsigned long long)g.ntris << iqr::kPieceBits)) ++key_bits;
+    if (npairs) {
+        for (int k = 0; k < 2; ++k) {
+            IQR_HIP(r->keys[k].reserve((size_t)npairs * sizeof(unsigned long long)));
+            IQR_HIP(r->vals[k].reserve((size_t)npairs * sizeof(uint32_t)));
+        }
+        IQR_HIP(iqr::launch_bin(s, fp, r->recs.as<iqr::setup_rec>(), nrec, key_bits, r->keys[in].as<unsigned long long>(),
+                                r->vals[in].as<uint32_t>()));
+    }
+    IQR_HIP(hipEventRecord(r->ev[3], s));
+    if (npairs) {
+        unsigned tile_bits = 1;
+        while ((1ull << tile_bits) < (unsigned long long)fp.ntx * fp.nty) ++tile_bits;
+        const unsigned end_bit = key_bits + tile_bits;
+        size_t need = 0;
+        IQR_HIP(iqr::sort_pairs(s, nullptr, need, r->keys[in].as<unsigned long long>(),
+                                r->keys[out].as<unsigned long long>(), r->vals[in].as<uint32_t>(),
+                                r->vals[out].as<uint32_t>(), npairs, end_bit));
+        IQR_HIP(r->sort_temp.reserve(std::max<size_t>(need, 16)));
+        need = r->sort_temp.bytes;
+        IQR_HIP(iqr::sort_pairs(s, r->sort_temp.p, need, r->keys[in].as<unsigned long long>(),
+                                r->keys[out].as<unsigned long long>(), r->vals[in].as<uint32_t>(),
+                                r->vals[out].as<uint32_t>(), npairs, end_bit));
+    }
+    IQR_HIP(iqr::launch_ranges(s, fp, r->keys[out].as<unsigned long long>(), npairs, key_bits, r->ranges.as<uint32_t>()));
+    IQR_HIP(hipEventRecord(r->ev[4], s));
+    IQR_HIP(iqr::launch_tiles(s, fp, r->recs.as<iqr::setup_rec>(), r->vals[out].as<uint32_t>(), r->ranges.as<uint32_t>(),
+                              r->frame.as<uint32_t>(), nullptr, nullptr));
+    IQR_HIP(hipEventRecord(r->ev[5], s));
+    r->pending = true;
+    r->have_frame = true;
+    r->last_nrec = nrec;
+    r->last_npairs = npairs;
+    r->last_ntris = g.ntris;
+    return IQPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iqpt_raster_create(int device, uint32_t width, uint32_t height, uint32_t samples, iqpt_raster** out) {
+    if (!out) return iqpt::fail(IQPT_ERR_INVALID_ARG, "out is NULL");
+    *out = nullptr;
+    if (width == 0 || height == 0 || width > IQPT_RASTER_MAX_DIM || height > IQPT_RASTER_MAX_DIM)
+        return iqpt::fail(IQPT_ERR_INVALID_ARG, "frame size must be 1..8192 in each dimension");
+    if (samples != 1 && samples != 4) return iqpt::fail(IQPT_ERR_INVALID_ARG, "samples must be 1 or 4");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+        return iqpt::fail(IQPT_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= count) return iqpt::fail(IQPT_ERR_NO_DEVICE, "device index out of range");
+
+    iqpt_raster* r = new iqpt_raster();
+    r->device = device;
+    r->fp.width = width;
+    r->fp.height = height;
+    r->fp.samples = samples;
+    r->fp.ntx = (width + iqr::kTile - 1) / iqr::kTile;
+    r->fp.nty = (height + iqr::kTile - 1) / iqr::kTile;
+    auto fail_with = [&](hipError_t e, const char* what) {
+        const int st = hip_fail(e, what);
+        iqpt_raster_destroy(r);
+        return st;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device)) != hipSuccess) return fail_with(e, "hipSetDevice");
+    if ((e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking)) != hipSuccess) return fail_with(e, "hipStreamCreate");
+    for (int k = 0; k < kEvents; ++k)
+        if ((e = hipEventCreate(&r->ev[k])) != hipSuccess) return fail_with(e, "hipEventCreate");
+    if ((e = hipHostMalloc((void**)&r->host_cnt, sizeof(iqr::counters), hipHostMallocDefault)) != hipSuccess)
+        return fail_with(e, "hipHostMalloc");
+    if ((e = r->cnt.reserve(sizeof(iqr::counters))) != hipSuccess) return fail_with(e, "hipMalloc(counters)");
+    if ((e = r->camera.reserve(32 * sizeof(float))) != hipSuccess) return fail_with(e, "hipMalloc(camera)");
+    if ((e = r->frame.reserve((size_t)width * height * 4)) != hipSuccess) return fail_with(e, "hipMalloc(frame)");
+    if ((e = r->ranges.reserve((size_t)r->fp.ntx * r->fp.nty * 8)) != hipSuccess) return fail_with(e, "hipMalloc(ranges)");
+    *out = r;
+    return IQPT_OK;
+}
+
+int iqpt_raster_destroy(iqpt_raster* r) {
+    if (!r) return IQPT_OK;
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    r->scene.release();
+    r->direct.release();
+    for (dbuf* b : {&r->camera, &r->recs, &r->cnt, &r->frame, &r->depth_samples, &r->prim_samples, &r->sort_temp,
+                    &r->keys[0], &r->keys[1], &r->vals[0], &r->vals[1], &r->ranges})
+        b->release();
+    if (r->host_cnt) (void)hipHostFree(r->host_cnt);
+    for (hipEvent_t ev : r->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    delete r;
+    return IQPT_OK;
+}
+
+int iqpt_raster_set_camera(iqpt_raster* r, const iqpt_camera* cam) {
+    if (!r || !cam) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (cam->width != r->fp.width || cam->height != r->fp.height)
+        return iqpt::fail(IQPT_ERR_INVALID_ARG, "camera size differs from the frame's");
+    if (int st = set_device(r)) return st;
+    float m[32];
+    std::memcpy(m, cam->view, 64);
+    std::memcpy(m + 16, cam->projection, 64);
+    // ordered behind the draws in flight; m is on the stack, so the copy is finished before returning
+    IQR_HIP(hipMemcpyAsync(r->camera.p, m, sizeof m, hipMemcpyHostToDevice, r->stream));
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    r->have_camera = true;
+    r->scene.transformed = false;
+    return IQPT_OK;
+}
+
+int iqpt_raster_upload_scene(iqpt_raster* r, const iqpt_scene* scene) {
+    if (!r || !scene) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    uint32_t n = 0;
+    if (int st = iqpt_scene_draw_list(scene, nullptr, 0, &n)) return st;
+    std::vector<iqpt_draw_item> items(n);
+    if (n)
+        if (int st = iqpt_scene_draw_list(scene, items.data(), n, &n)) return st;
+
+    // one copy of every distinct mesh in the pools; one draw record per model
+    std::vector<float> verts;
+    std::vector<uint32_t> indices, vend, tend;
+    std::vector<iqr::draw_rec> draws;
+    struct pooled { const iqpt_vertex* v; uint32_t vbase, ibase; };
+    std::vector<pooled> pool;
+    uint64_t nverts = 0, ntris = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const iqpt_draw_item& it = items[i];
+        if (it.num_indices % 3) return iqpt::fail(IQPT_ERR_INVALID_ARG, "model " + std::to_string(i) + ": index count is not a multiple of 3");
+        if (it.num_indices == 0 || it.num_vertices == 0) continue;      // an empty mesh draws nothing
+        const pooled* found = nullptr;
+        for (const pooled& p : pool)
+            if (p.v == it.vertices) found = &p;
+        if (!found) {
+            for (uint32_t k = 0; k < it.num_indices; ++k)
+                if (it.indices[k] >= it.num_vertices)
+                    return iqpt::fail(IQPT_ERR_INVALID_ARG, "model " + std::to_string(i) + ": index out of range");
+            pool.push_back({it.vertices, (uint32_t)(verts.size() / 6), (uint32_t)indices.size()});
+            const float* f = reinterpret_cast<const float*>(it.vertices);
+            verts.insert(verts.end(), f, f + 6 * (size_t)it.num_vertices);
+            indices.insert(indices.end(), it.indices, it.indices + it.num_indices);
+            found = &pool.back();
+        }
+        iqr::draw_rec d{};
+        std::memcpy(d.model, it.transform, sizeof d.model);
+        const iq::mat4 N = iq::normal_matrix(iq::mat4::from(it.transform));      // path_tracer.cu:260
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 4; ++b) d.normal[a * 4 + b] = N.m[a][b];
+        d.albedo[0] = it.albedo[0]; d.albedo[1] = it.albedo[1]; d.albedo[2] = it.albedo[2]; d.albedo[3] = 1.0f;
+        d.vbase = (uint32_t)nverts;
+        d.src_vbase = found->vbase;
+        d.ibase = found->ibase;
+        d.tbase = (uint32_t)ntris;
+        nverts += it.num_vertices;
+        ntris += it.num_indices / 3;
+        if (ntris >= iqr::kMaxTriangles || nverts >= 0x7fffffffu)
+            return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^28 triangles in one frame");
+        draws.push_back(d);
+        vend.push_back((uint32_t)nverts);
+        tend.push_back((uint32_t)ntris);
+    }
+
+    if (int st = set_device(r)) return st;
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    geometry& g = r->scene;
+    hipStream_t s = r->stream;
+    if (int st = upload(g.draws, draws.data(), draws.size() * sizeof(iqr::draw_rec), s)) return st;
+    if (int st = upload(g.vend, vend.data(), vend.size() * 4, s)) return st;
+    if (int st = upload(g.tend, tend.data(), tend.size() * 4, s)) return st;
+    if (int st = upload(g.indices, indices.data(), indices.size() * 4, s)) return st;
+    if (int st = upload(g.mesh_verts, verts.data(), verts.size() * 4, s)) return st;
+    IQR_HIP(g.clip.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
+    IQR_HIP(g.wn.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
+    IQR_HIP(hipStreamSynchronize(s));              // the host vectors go out of scope
+    g.ndraws = (uint32_t)draws.size();
+    g.nverts = (uint32_t)nverts;
+    g.ntris = (uint32_t)ntris;
+    g.transformed = false;
+    r->have_scene = true;
+    return IQPT_OK;
+}
+
+int iqpt_raster_draw(iqpt_raster* r) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if (!r->have_camera || !r->have_scene) return iqpt::fail(IQPT_ERR_NOT_READY, "draw before set_camera / upload_scene");
+    return run_draw(r, r->scene, true);
+}
+
+int iqpt_raster_draw_clip(iqpt_raster* r, const float* clip_xyzw, const float* normals, uint32_t nverts,
+                          const uint32_t* indices, uint32_t nindices) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if ((nverts && (!clip_xyzw || !normals)) || (nindices && !indices))
+        return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL vertex / index array");
+    if (nindices % 3) return iqpt::fail(IQPT_ERR_INVALID_ARG, "index count is not a multiple of 3");
+    if (nindices / 3 >= iqr::kMaxTriangles) return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^28 triangles in one frame");
+    for (uint32_t k = 0; k < nindices; ++k)
+        if (indices[k] >= nverts) return iqpt::fail(IQPT_ERR_INVALID_ARG, "index out of range");
+    if (int st = set_device(r)) return st;
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    std::vector<float> c4((size_t)nverts * 4), n4((size_t)nverts * 4, 0.0f);
+    if (nverts) std::memcpy(c4.data(), clip_xyzw, c4.size() * 4);
+    for (uint32_t i = 0; i < nverts; ++i)
+        for (int k = 0; k < 3; ++k) n4[(size_t)i * 4 + k] = normals[(size_t)i * 3 + k];
+    iqr::draw_rec d{};
+    d.albedo[0] = 1.0f; d.albedo[3] = 1.0f;                                       // pixel_shader.hlsl: albedo
+    const uint32_t ntris = nindices / 3;
+    geometry& g = r->direct;
+    hipStream_t s = r->stream;
+    if (int st = upload(g.draws, &d, sizeof d, s)) return st;
+    if (int st = upload(g.vend, &nverts, 4, s)) return st;
+    if (int st = upload(g.tend, &ntris, 4, s)) return st;
+    if (int st = upload(g.indices, indices, (size_t)nindices * 4, s)) return st;
+    if (int st = upload(g.clip, c4.data(), c4.size() * 4, s)) return st;
+    if (int st = upload(g.wn, n4.data(), n4.size() * 4, s)) return st;
+    IQR_HIP(hipStreamSynchronize(s));
+    g.ndraws = 1;
+    g.nverts = nverts;
+    g.ntris = ntris;
+    return run_draw(r, g, false);
+}
+
+int iqpt_raster_read(iqpt_raster* r, uint8_t* bgra, float* depth_samples, uint32_t* prim_samples) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if (!r->have_frame) return iqpt::fail(IQPT_ERR_NOT_READY, "read before the first draw");
+    if (int st = set_device(r)) return st;
+    hipStream_t s = r->stream;
+    const size_t npix = (size_t)r->fp.width * r->fp.height, nsamp = npix * r->fp.samples;
+    if (depth_samples || prim_samples) {
+        // the tile kernel of the last draw again, over the same sorted lists, with the per-sample outputs on
+        IQR_HIP(r->depth_samples.reserve(nsamp * 4));
+        IQR_HIP(r->prim_samples.reserve(nsamp * 4));
+        IQR_HIP(iqr::launch_tiles(s, r->fp, r->recs.as<iqr::setup_rec>(), r->vals[1].as<uint32_t>(),
+                                  r->ranges.as<uint32_t>(), r->frame.as<uint32_t>(), r->depth_samples.as<float>(),
+                                  r->prim_samples.as<uint32_t>()));
+        if (depth_samples) IQR_HIP(hipMemcpyAsync(depth_samples, r->depth_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
+        if (prim_samples) IQR_HIP(hipMemcpyAsync(prim_samples, r->prim_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (bgra) IQR_HIP(hipMemcpyAsync(bgra, r->frame.p, npix * 4, hipMemcpyDeviceToHost, s));
+    IQR_HIP(hipStreamSynchronize(s));
+    return IQPT_OK;
+}
+
+int iqpt_raster_copy_frame_device(iqpt_raster* r, void* dst_device, size_t bytes) {
+    if (!r || !dst_device) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (!r->have_frame) return iqpt::fail(IQPT_ERR_NOT_READY, "copy before the first draw");
+    if (bytes != (size_t)r->fp.width * r->fp.height * 4) return iqpt::fail(IQPT_ERR_INVALID_ARG, "bytes must be width*height*4");
+    if (int st = set_device(r)) return st;
+    IQR_HIP(hipMemcpyAsync(dst_device, r->frame.p, bytes, hipMemcpyDeviceToDevice, r->stream));
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    return IQPT_OK;
+}
+
+int iqpt_raster_sync(iqpt_raster* r) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if (int st = set_device(r)) return st;
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    return IQPT_OK;
+}
+
+int iqpt_raster_time(iqpt_raster* r, double* total_ms, uint64_t* draws) {
+    if (!r || !total_ms || !draws) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (int st = set_device(r)) return st;
+    if (int st = collect(r)) return st;
+    *total_ms = r->total_ms;
+    *draws = r->draws;
+    r->total_ms = 0.0;
+    r->draws = 0;
+    for (double& v : r->stage_ms) v = 0.0;
+    return IQPT_OK;
+}
+
+int iqpt_raster_stage_time(iqpt_raster* r, double stage_ms[5]) {
+    if (!r || !stage_ms) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (int st = set_device(r)) return st;
+    if (int st = collect(r)) return st;
+    for (int k = 0; k < 5; ++k) stage_ms[k] = r->stage_ms[k];
+    return IQPT_OK;
+}
+
+int iqpt_raster_stats(iqpt_raster* r, uint64_t counts[3]) {
+    if (!r || !counts) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    counts[0] = r->last_ntris;
+    counts[1] = r->last_nrec;
+    counts[2] = r->last_npairs;
+    return IQPT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,115 @@
+// rasterizer.cpp — the facade of raster/rasterizer.hpp (IoniqRE/rasterizer.cu:8-23, 128-175; renderer.cu:18-78;
+// shader.cu:48-60).
+#include "raster/rasterizer.hpp"
+
+#include <cstring>
+
+#include "iq_host_math.hpp"
+
+namespace iqpt {
+
+namespace {
+rasterizer* g_rasterizer = nullptr;
+renderer* g_renderer = nullptr;
+}  // namespace
+
+void shader::update_view_proj(const float view[16], const float proj[16]) {      // shader.cu:55-60
+    std::memcpy(m_view, view, sizeof m_view);
+    std::memcpy(m_proj, proj, sizeof m_proj);
+    m_has_view_proj = true;
+}
+
+void shader::update_transform(const float tr[16]) {                              // shader.cu:48-53
+    std::memcpy(m_model, tr, sizeof m_model);
+    const iq::mat4 n = iq::normal_matrix(iq::mat4::from(tr));
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 4; ++b) m_normal[a * 4 + b] = n.m[a][b];
+}
+
+void rasterizer::init(camera* cam, const rasterizer_options& opt) {
+    if (!g_rasterizer) g_rasterizer = new rasterizer(cam, opt);
+}
+void rasterizer::shutdown() {
+    delete g_rasterizer;
+    g_rasterizer = nullptr;
+}
+rasterizer* rasterizer::get() { return g_rasterizer; }
+
+rasterizer::rasterizer(camera* cam, const rasterizer_options& opt) : m_camera(cam), m_opt(opt) {
+    const uint32_t w = cam->get_width(), h = cam->get_height();
+    IQPT_THROW_FAILED(iqpt_raster_create(opt.device, w, h, opt.samples, &m_r));
+    m_host_pixels.assign((size_t)w * h, path_tracer::pixel{0, 0, 0, 0});
+}
+
+rasterizer::~rasterizer() { iqpt_raster_destroy(m_r); }
+
+void rasterizer::begin_frame() {}
+
+void rasterizer::end_frame() {
+    if (!m_drawn) return;
+    IQPT_THROW_FAILED(iqpt_raster_read(m_r, reinterpret_cast<uint8_t*>(m_host_pixels.data()), nullptr, nullptr));
+    if (!m_opt.ppm_path.empty())
+        IQPT_THROW_FAILED(iqpt_write_ppm(m_opt.ppm_path.c_str(), m_camera->get_width(), m_camera->get_height(),
+                                         reinterpret_cast<const uint8_t*>(m_host_pixels.data())));
+    m_drawn = false;
+}
+
+void rasterizer::draw_scene(const scene& scn, std::vector<shader>& shaders, float /*dt*/) {   // rasterizer.cu:160-175
+    // the view and projection are the shader's once the application set them (shader.cu:55-60), else the camera's
+    iqpt_camera cam = m_camera->raw();
+    if (!shaders.empty() && shaders[0].has_view_proj()) {
+        std::memcpy(cam.view, shaders[0].view(), sizeof cam.view);
+        std::memcpy(cam.projection, shaders[0].projection(), sizeof cam.projection);
+    }
+    IQPT_THROW_FAILED(iqpt_raster_set_camera(m_r, &cam));
+    if (!m_have_scene || scn.revision() != m_scene_revision) {
+        // mesh::setup_mesh's buffers and every model's transform, once per scene change; scene::modified() is
+        // left for the path tracer, whose own packet is built from it when that engine draws next
+        IQPT_THROW_FAILED(iqpt_raster_upload_scene(m_r, scn.handle()));
+        m_have_scene = true;
+        m_scene_revision = scn.revision();
+    }
+    IQPT_THROW_FAILED(iqpt_raster_draw(m_r));
+    m_drawn = true;
+    m_frames += 1;
+}
+
+void renderer::init(camera* cam, const renderer_options& opt) {                  // renderer.cu:18-26
+    if (!g_renderer) {
+        rasterizer::init(cam, opt.rasterizer);
+        path_tracer::init(cam, opt.path_tracer);
+        g_renderer = new renderer();
+    }
+}
+
+void renderer::shutdown() {                                                      // renderer.cu:28-37
+    if (g_renderer) {
+        path_tracer::shutdown();
+        rasterizer::shutdown();
+        delete g_renderer;
+        g_renderer = nullptr;
+    }
+}
+
+renderer* renderer::get() { return g_renderer; }
+
+renderer::renderer() : m_engine_idx(engine::PATHTRACER) {                        // renderer.cu:70-78
+    m_new_engine = m_engine_idx;
+    m_engines[0] = rasterizer::get();
+    m_engines[1] = path_tracer::get();
+}
+
+void renderer::begin_frame() {                                                   // renderer.cu:45-53
+    if (m_new_engine != m_engine_idx) m_engine_idx = m_new_engine;
+    m_engines[(size_t)m_engine_idx]->begin_frame();
+}
+
+void renderer::end_frame() { m_engines[(size_t)m_engine_idx]->end_frame(); }
+
+void renderer::draw_scene(const scene& scn, std::vector<shader>& shaders, float dt) {
+    m_engines[(size_t)m_engine_idx]->draw_scene(scn, shaders, dt);
+}
+
+void renderer::reset() { static_cast<path_tracer*>(m_engines[1])->reset(); }    // renderer.cu:65-68
+
+}  // namespace iqpt

@@ -3,6 +3,7 @@
 // fixed dt, and dumps the frame as PPM (the D3D11 present path, path_tracer.cu:171-210, is out of
 // scope). Usage:
 //   iqpt_cli --preset cornell --width 1920 --height 1080 --spp 64 --max-depth 8 --out cornell.ppm
+//   iqpt_cli --engine raster --preset cornell --samples 4 --out preview.ppm     (the rasterized preview)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,10 +11,11 @@
 #include <vector>
 
 #include "path_tracer.hpp"
+#include "raster/rasterizer.hpp"
 
 int main(int argc, char** argv) {
-    std::string preset = "cornell", out = "iqpt.ppm";
-    int width = 640, height = 360, spp = 16, launches = 1, max_depth = 8, device = 0;
+    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt";
+    int width = 640, height = 360, spp = 16, launches = 1, max_depth = 8, device = 0, samples = 4;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
         const char* v = argv[i + 1];
@@ -25,15 +27,43 @@ int main(int argc, char** argv) {
         else if (k == "--launches") launches = std::atoi(v);
         else if (k == "--max-depth") max_depth = std::atoi(v);
         else if (k == "--device") device = std::atoi(v);
+        else if (k == "--engine") engine = v;
+        else if (k == "--samples") samples = std::atoi(v);
         else {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
             return 2;
         }
     }
+    if (engine != "pt" && engine != "raster") {
+        std::fprintf(stderr, "--engine must be pt or raster\n");
+        return 2;
+    }
     try {
         iqpt::camera cam((uint16_t)width, (uint16_t)height);
         iqpt::scene scn;
         scn.add_preset(preset);
+        if (engine == "raster") {
+            // the other engine (rasterizer.cu): one rasterized frame, presented as PPM by end_frame
+            iqpt::rasterizer_options ro;
+            ro.device = device;
+            ro.samples = (uint32_t)samples;
+            ro.ppm_path = out;
+            iqpt::rasterizer::init(&cam, ro);
+            iqpt::rasterizer* rs = iqpt::rasterizer::get();
+            std::vector<iqpt::shader> sh(1);
+            rs->begin_frame();
+            rs->draw_scene(scn, sh, 0.0f);
+            rs->end_frame();
+            double ms = 0.0;
+            uint64_t draws = 0, counts[3] = {};
+            IQPT_THROW_FAILED(iqpt_raster_time(rs->context(), &ms, &draws));
+            IQPT_THROW_FAILED(iqpt_raster_stats(rs->context(), counts));
+            std::printf("{\"preset\": \"%s\", \"engine\": \"raster\", \"samples\": %d, \"draws\": %llu, "
+                        "\"triangles\": %llu, \"draw_ms\": %.4f, \"out\": \"%s\"}\n",
+                        preset.c_str(), samples, (unsigned long long)draws, (unsigned long long)counts[0], ms, out.c_str());
+            iqpt::rasterizer::shutdown();
+            return 0;
+        }
         iqpt::path_tracer_options opt;
         opt.device = device;
         opt.max_depth = max_depth;

@@ -32,6 +32,7 @@ ORACLE_GLIBC_LIB = ORACLE_DIR / "liboracle_glibc.so"
 ORACLE_FMA_LIB = ORACLE_DIR / "liboracle_fma.so"      # informational: contraction on + glibc libm (nvcc-like)
 CLI_PATH = PKG_DIR / "iqpt_cli"
 FACADE_TEST_PATH = PKG_DIR / "test_facade"
+RASTER_FACADE_TEST_PATH = PKG_DIR / "test_raster_facade"
 
 ARCH = os.environ.get("IQPT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
@@ -42,7 +43,9 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", *FP_FLAGS,
              "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function",
              f"-I{INCLUDE}", f"-I{CSRC}"]
 
-LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tracer.cpp"]
+LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tracer.cpp",
+               # the rasterizer: its own directory, outside kernel_source_sha16's path-tracing identity
+               "raster/iq_raster_kernels.hip", "raster/iq_raster.cpp", "raster/rasterizer.cpp"]
 
 
 def _run(cmd: list[str], cwd: Path | None = None) -> None:
@@ -61,6 +64,15 @@ def _newer(target: Path, deps: list[Path]) -> bool:
 
 def _headers() -> list[Path]:
     return sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
+
+
+def _raster_headers() -> list[Path]:
+    return sorted((CSRC / "raster").glob("*.hpp")) + sorted((INCLUDE / "raster").glob("*.h"))
+
+
+def _deps() -> list[Path]:
+    """Every header a library object or a tool may include."""
+    return _headers() + _raster_headers()
 
 
 def kernel_source_sha16() -> str:
@@ -82,7 +94,7 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
     ``flags``/``target``: extra compiler flags into another library (compiler-option A/B runs)."""
     target = target or (STATS_LIB_PATH if stats else LIB_PATH)
     srcs = [CSRC / s for s in LIB_SOURCES]
-    if not force and _newer(target, srcs + _headers() + [Path(__file__)]):
+    if not force and _newer(target, srcs + _deps() + [Path(__file__)]):
         return target
     bdir = BUILD_DIR / (target.stem if flags else ("stats" if stats else "prod"))
     bdir.mkdir(parents=True, exist_ok=True)
@@ -92,7 +104,7 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
     for s in srcs:
         o = bdir / (s.name + ".o")
         # an object is rebuilt when its source, a header or this recipe is newer (force: always)
-        if force or not _newer(o, [s] + _headers() + [Path(__file__)]):
+        if force or not _newer(o, [s] + _deps() + [Path(__file__)]):
             cmds.append([HIPCC, *HIP_FLAGS, *extra, "-x", "hip", "-c", str(s), "-o", str(o)])
         objs.append(o)
     if cmds:
@@ -105,14 +117,15 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
 
 
 def build_tools(force: bool = False) -> list[Path]:
-    """C++ programs over the path_tracer facade: the headless CLI and the facade test."""
+    """C++ programs over the facades: the headless CLI, the path_tracer facade test and the two-engine renderer test."""
     lib = build_lib(force)
     out = []
     for src, dst in ((CSRC / "tools" / "iqpt_cli.cpp", CLI_PATH),
-                     (CSRC / "tools" / "test_facade.cpp", FACADE_TEST_PATH)):
+                     (CSRC / "tools" / "test_facade.cpp", FACADE_TEST_PATH),
+                     (CSRC / "tools" / "test_raster_facade.cpp", RASTER_FACADE_TEST_PATH)):
         if not src.exists():
             continue
-        if force or not _newer(dst, [src, lib] + _headers()):
+        if force or not _newer(dst, [src, lib] + _deps()):
             _run([HIPCC, "-O2", "-std=c++17", *FP_FLAGS, f"-I{INCLUDE}", f"-I{CSRC}", str(src),
                   f"-L{PKG_DIR}", "-liqpt", f"-Wl,-rpath,$ORIGIN", "-o", str(dst)])
         out.append(dst)

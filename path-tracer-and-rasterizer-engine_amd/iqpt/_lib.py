@@ -84,6 +84,16 @@ class PixelSet(C.Structure):
                 ("ystep", C.c_uint32), ("nrows", C.c_uint32)]
 
 
+class DrawItem(C.Structure):
+    """iqpt_draw_item (include/raster/iqpt_raster.h): one model in draw order, with its mesh data."""
+    _fields_ = [("transform", C.c_float * 16), ("vertices", C.POINTER(Vertex)), ("indices", C.POINTER(C.c_uint32)),
+                ("num_vertices", C.c_uint32), ("num_indices", C.c_uint32), ("albedo", C.c_float * 3),
+                ("mesh_type", C.c_int32)]
+
+
+RASTER_NO_PRIM = 0xFFFFFFFF                    # IQPT_RASTER_NO_PRIM
+RASTER_MAX_DIM = 8192                          # IQPT_RASTER_MAX_DIM
+
 # (name, restype, argtypes) of every entry point declared in include/iqpt.h
 _P = C.c_void_p
 _FP = C.POINTER(C.c_float)
@@ -141,6 +151,22 @@ SIGNATURES = [
     ("iqpt_scene_set_model_material", C.c_int, [_P, C.c_char_p, C.c_uint32]),
     ("iqpt_scene_build_packet", C.c_int, [_P, C.POINTER(PacketDesc)]),
 ]
+# the same for include/raster/iqpt_raster.h (the rasterizer's additions; IQPT_ABI_VERSION is unchanged by them)
+RASTER_SIGNATURES = [
+    ("iqpt_scene_draw_list", C.c_int, [_P, C.POINTER(DrawItem), C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("iqpt_raster_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_raster_destroy", C.c_int, [_P]),
+    ("iqpt_raster_set_camera", C.c_int, [_P, C.POINTER(Camera)]),
+    ("iqpt_raster_upload_scene", C.c_int, [_P, _P]),
+    ("iqpt_raster_draw", C.c_int, [_P]),
+    ("iqpt_raster_draw_clip", C.c_int, [_P, _FP, _FP, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
+    ("iqpt_raster_read", C.c_int, [_P, C.POINTER(C.c_uint8), _FP, C.POINTER(C.c_uint32)]),
+    ("iqpt_raster_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_raster_sync", C.c_int, [_P]),
+    ("iqpt_raster_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("iqpt_raster_stage_time", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("iqpt_raster_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+]
 
 _lib = None
 
@@ -166,7 +192,7 @@ def load() -> C.CDLL:
     abi = lib.iqpt_abi_version() if getattr(lib, "iqpt_abi_version", None) is not None else None
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
-    for name, res, args in SIGNATURES:
+    for name, res, args in SIGNATURES + RASTER_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:

@@ -93,6 +93,23 @@ class Scene:
         check(self._lib.iqpt_scene_num_meshes(self._h, C.byref(n)), "num_meshes")
         return n.value
 
+    def draw_list(self) -> list[dict]:
+        """The models in draw order with their mesh data (iqpt_scene_draw_list; both mesh types): dicts of
+        transform [4,4] float32, vertices [n,6] float32 (pos, normal), indices uint32, albedo [3], mesh_type."""
+        n = C.c_uint32()
+        check(self._lib.iqpt_scene_draw_list(self._h, None, 0, C.byref(n)), "iqpt_scene_draw_list")
+        items = (_lib.DrawItem * max(n.value, 1))()
+        check(self._lib.iqpt_scene_draw_list(self._h, items, n.value, C.byref(n)), "iqpt_scene_draw_list")
+        out = []
+        for it in items[:n.value]:
+            v = (np.ctypeslib.as_array(C.cast(it.vertices, C.POINTER(C.c_float)), (it.num_vertices, 6)).copy()
+                 if it.num_vertices else np.zeros((0, 6), np.float32))
+            i = (np.ctypeslib.as_array(it.indices, (it.num_indices,)).copy() if it.num_indices
+                 else np.zeros(0, np.uint32))
+            out.append({"transform": np.array(it.transform, np.float32).reshape(4, 4), "vertices": v, "indices": i,
+                        "albedo": np.array(it.albedo, np.float32), "mesh_type": int(it.mesh_type)})
+        return out
+
     def build_packet(self) -> PacketDesc:
         pk = PacketDesc()
         check(self._lib.iqpt_scene_build_packet(self._h, C.byref(pk)), "build_packet")

@@ -814,11 +814,75 @@ __device__ __forceinline__ void test_sphere_pair2(const float4 s0, const float4 
     if (tb && second && !(db.y < 0.0f)) sphere_roots<OPT>(hbb.y, db.y, cb, kb, ib, k + 1);
 }
 
+// Two triangle pairs (k0, k0+1) and (k1, k1+1), k0 < k1, for one ray (IQPT_PAIR2_TWO): both pairs' records are read
+// together and their stages interleaved, so two dependent chains stay in flight where only ray a needs the pairs. Each
+// pair sees exactly the operation sequence of test_triangle_pair (a stage both pairs have left is skipped, as there)
+// and the closest hit is updated in index order. The first pair is never the packet's odd tail.
+template <int OPT>
+__device__ __forceinline__ void test_triangle_pair_x2(const float4* q, const float4* s, const ray3 r, bool ta,
+                                                      float& closest, int& kind, uint32_t& idx, uint32_t k0,
+                                                      uint32_t k1, bool second1) {
+    if (ta) stat_add<OPT>(0, 4u);
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+    const float4 s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3], s4 = s[4];
+    const f2 v0xq = {q0.x, q0.y}, v0yq = {q0.z, q0.w}, v0zq = {q1.x, q1.y};
+    const f2 e1xq = {q1.z, q1.w}, e1yq = {q2.x, q2.y}, e1zq = {q2.z, q2.w};
+    const f2 e2xq = {q3.x, q3.y}, e2yq = {q3.z, q3.w}, e2zq = {q4.x, q4.y};
+    const f2 v0xs = {s0.x, s0.y}, v0ys = {s0.z, s0.w}, v0zs = {s1.x, s1.y};
+    const f2 e1xs = {s1.z, s1.w}, e1ys = {s2.x, s2.y}, e1zs = {s2.z, s2.w};
+    const f2 e2xs = {s3.x, s3.y}, e2ys = {s3.z, s3.w}, e2zs = {s4.x, s4.y};
+    const f2 pxq = r.dy * e2zq - r.dz * e2yq, pxs = r.dy * e2zs - r.dz * e2ys;
+    const f2 pyq = r.dz * e2xq - r.dx * e2zq, pys = r.dz * e2xs - r.dx * e2zs;
+    const f2 pzq = r.dx * e2yq - r.dy * e2xq, pzs = r.dx * e2ys - r.dy * e2xs;
+    const f2 detq = (e1xq * pxq + e1yq * pyq) + e1zq * pzq, dets = (e1xs * pxs + e1ys * pys) + e1zs * pzs;
+    bool a0 = ta && !(iq_fabsf(detq.x) < 0.000001f), a1 = ta && !(iq_fabsf(detq.y) < 0.000001f);
+    bool b0 = ta && !(iq_fabsf(dets.x) < 0.000001f), b1 = ta && second1 && !(iq_fabsf(dets.y) < 0.000001f);
+    if (!(a0 || a1 || b0 || b1)) return;
+    const f2 invq = {rcp_scene<OPT>(detq.x), rcp_scene<OPT>(detq.y)};
+    const f2 invs = {rcp_scene<OPT>(dets.x), rcp_scene<OPT>(dets.y)};
+    const f2 txq = r.ox - v0xq, tyq = r.oy - v0yq, tzq = r.oz - v0zq;
+    const f2 txs = r.ox - v0xs, tys = r.oy - v0ys, tzs = r.oz - v0zs;
+    const f2 uq = ((txq * pxq + tyq * pyq) + tzq * pzq) * invq, us = ((txs * pxs + tys * pys) + tzs * pzs) * invs;
+    a0 = a0 && !(uq.x < 0.0f || uq.x > 1.0f);
+    a1 = a1 && !(uq.y < 0.0f || uq.y > 1.0f);
+    b0 = b0 && !(us.x < 0.0f || us.x > 1.0f);
+    b1 = b1 && !(us.y < 0.0f || us.y > 1.0f);
+    if (!(a0 || a1 || b0 || b1)) return;
+    const f2 qxq = tyq * e1zq - tzq * e1yq, qxs = tys * e1zs - tzs * e1ys;
+    const f2 qyq = tzq * e1xq - txq * e1zq, qys = tzs * e1xs - txs * e1zs;
+    const f2 qzq = txq * e1yq - tyq * e1xq, qzs = txs * e1ys - tys * e1xs;
+    const f2 vq = ((r.dx * qxq + r.dy * qyq) + r.dz * qzq) * invq;
+    const f2 vs = ((r.dx * qxs + r.dy * qys) + r.dz * qzs) * invs;
+    const f2 uvq = uq + vq, uvs = us + vs;
+    a0 = a0 && !(vq.x < 0.0f || uvq.x > 1.0f);
+    a1 = a1 && !(vq.y < 0.0f || uvq.y > 1.0f);
+    b0 = b0 && !(vs.x < 0.0f || uvs.x > 1.0f);
+    b1 = b1 && !(vs.y < 0.0f || uvs.y > 1.0f);
+    if (!(a0 || a1 || b0 || b1)) return;
+    const f2 t_q = ((e2xq * qxq + e2yq * qyq) + e2zq * qzq) * invq;
+    const f2 t_s = ((e2xs * qxs + e2ys * qys) + e2zs * qzs) * invs;
+    if (a0 && !(t_q.x < kTMin || closest < t_q.x)) { closest = t_q.x; kind = kHitTri; idx = k0; }
+    if (a1 && !(t_q.y < kTMin || closest < t_q.y)) { closest = t_q.y; kind = kHitTri; idx = k0 + 1; }
+    if (b0 && !(t_s.x < kTMin || closest < t_s.x)) { closest = t_s.x; kind = kHitTri; idx = k1; }
+    if (b1 && !(t_s.y < kTMin || closest < t_s.y)) { closest = t_s.y; kind = kHitTri; idx = k1 + 1; }
+}
+
 // The closest hits of rays a and b over the LDS-resident pairs (kOptCull): ray b is always a camera ray and
 // tests the pairs of the wave's OR of its lanes' tile masks (or the uniform tile's own mask, as
 // intersect_culled); ray a tests the same pairs when every active lane's ray a is a camera ray, else every
 // pair (all_a). The loop runs over the union in index order, so each ray meets its pairs in the
 // reference's order. Called by all lanes of the wave.
+// The body is chosen per pair, wave-uniformly: the two-ray body only where ray b needs the pair (the pair is in its
+// mask and some lane of the wave has a ray b), else the one-ray body on ray a alone, so ray b's arithmetic is not
+// issued for nothing. IQPT_PAIR2_BOTH=1 sends every pair through the two-ray body (the form before; A/B builds).
+// IQPT_PAIR2_TWO=1 takes consecutive a-only triangle pairs two at a time (test_triangle_pair_x2). `st` (kOptStats):
+// [0], [1] triangle / sphere pairs visited, [2] one-ray triangle pair bodies among them.
+#ifndef IQPT_PAIR2_BOTH
+#define IQPT_PAIR2_BOTH 0
+#endif
+#ifndef IQPT_PAIR2_TWO
+#define IQPT_PAIR2_TWO 0
+#endif
 template <int OPT>
 __device__ __forceinline__ void intersect_culled2(const float4* tri, uint32_t ntri, const float4* sph, uint32_t nsph,
                                                   const uint32_t* lane_mask, uint32_t cm_t, uint32_t cm_s, bool all_a,
@@ -826,6 +890,7 @@ __device__ __forceinline__ void intersect_culled2(const float4* tri, uint32_t nt
                                                   int& ka, uint32_t& ia, float& cb, int& kb, uint32_t& ib, uint32_t wt,
                                                   const uint32_t* uni_mask, unsigned long long* st = nullptr) {
     const uint32_t tp = (ntri + 1) / 2, sp = (nsph + 1) / 2;
+    const bool any_b = IQPT_PAIR2_BOTH || __any(act_b);   // wave-uniform: some lane traces a ray b
     for (uint32_t w = 0; w * 32u < tp; ++w) {
         const uint32_t mb = uni_mask ? (w == 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cm_t) : uni_mask[w])
                                      : wave_or(lane_mask ? (w == 0 ? cm_t : lane_mask[w]) : 0u);
@@ -838,8 +903,25 @@ __device__ __forceinline__ void intersect_culled2(const float4* tri, uint32_t nt
             if (j >= tp) break;
             const bool in_b = (mb >> bit) & 1u;
             const float4* q = tri + (size_t)j * kTriPairFloat4;
-            test_triangle_pair2<OPT>(q[0], q[1], q[2], q[3], q[4], ra, rb, act_a, act_b && in_b, ca, ka, ia, cb, kb, ib,
-                                     2 * j, 2 * j + 1 < ntri);
+            if (IQPT_PAIR2_BOTH || (in_b && any_b)) {
+                test_triangle_pair2<OPT>(q[0], q[1], q[2], q[3], q[4], ra, rb, act_a, act_b && in_b, ca, ka, ia, cb, kb,
+                                         ib, 2 * j, 2 * j + 1 < ntri);
+                continue;
+            }
+            if (IQPT_PAIR2_TWO && m) {
+                // the next pair of the word is a-only too: both in one body
+                const uint32_t bit2 = (uint32_t)__builtin_ctz(m);
+                const uint32_t j2 = w * 32u + bit2;
+                if (j2 < tp && !(((mb >> bit2) & 1u) && any_b)) {
+                    m &= m - 1u;
+                    if ((OPT & kOptStats) && st) st[2] += 2ull;
+                    test_triangle_pair_x2<OPT>(q, tri + (size_t)j2 * kTriPairFloat4, ra, act_a, ca, ka, ia, 2 * j, 2 * j2,
+                                               2 * j2 + 1 < ntri);
+                    continue;
+                }
+            }
+            if ((OPT & kOptStats) && st) st[2] += 1ull;
+            if (act_a) test_triangle_pair<OPT>(q[0], q[1], q[2], q[3], q[4], ra, ca, ka, ia, 2 * j, 2 * j + 1 < ntri);
         }
     }
     for (uint32_t w = 0; w * 32u < sp; ++w) {
@@ -854,8 +936,12 @@ __device__ __forceinline__ void intersect_culled2(const float4* tri, uint32_t nt
             if (j >= sp) break;
             const bool in_b = (mb >> bit) & 1u;
             const float4* q = sph + (size_t)j * kSphPairFloat4;
-            test_sphere_pair2<OPT>(q[0], q[1], ra, rb, act_a, act_b && in_b, ca, ka, ia, cb, kb, ib, 2 * j,
-                                   2 * j + 1 < nsph);
+            if (IQPT_PAIR2_BOTH || (in_b && any_b)) {
+                test_sphere_pair2<OPT>(q[0], q[1], ra, rb, act_a, act_b && in_b, ca, ka, ia, cb, kb, ib, 2 * j,
+                                       2 * j + 1 < nsph);
+            } else if (act_a) {
+                test_sphere_pair<OPT>(q[0], q[1], ra, ca, ka, ia, 2 * j, 2 * j + 1 < nsph);
+            }
         }
     }
 }
@@ -1369,7 +1455,8 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                        s_term_lanes = 0;
     // kOptPipe: iterations whose one scatter served both ray a's sphere hits and promoted ray b's
     unsigned long long s_scatter_both = 0;
-    unsigned long long s_tests[2] = {0, 0};   // wave-level triangle / sphere pair tests (culled resident path)
+    // wave-level triangle / sphere pair tests (culled resident path); [2] kOptPipe: one-ray triangle pair bodies among [0]
+    unsigned long long s_tests[3] = {0, 0, 0};
     unsigned long long s_full = 0;            // iterations forced to the full loop (a secondary ray in the wave)
     unsigned long long s_refill = 0, s_refill_lanes = 0;   // refills that started pixels, pixels started
     unsigned long long s_spec_lanes = 0;      // kOptSplit: speculative slots started by this wave
@@ -2466,6 +2553,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
             atomicAdd(p.stats + 12, s_refill);
             atomicAdd(p.stats + 13, s_refill_lanes);
             atomicAdd(p.stats + 22, s_scatter_both);
+            atomicAdd(p.stats + 23, s_tests[2]);
         }
         {
             // BVH work and the primitive tests executed, summed over the wave's lanes

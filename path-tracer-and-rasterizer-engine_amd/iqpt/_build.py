@@ -173,10 +173,27 @@ def build_oracle_native() -> tuple[Path, str]:
     return dst, " ".join([Path(CC).name, *ORACLE_NATIVE_FLAGS, "-lm"])
 
 
+# The two-ray kernel with every pair through the two-ray body (the form before the per-pair body choice, DESIGN.md
+# §3.14): an A/B library for bench.py --lib and the tools' --lib, and the other side of tests/test_gpu_pair_bodies.py.
+PAIR2_BOTH_FLAGS = ("-DIQPT_PAIR2_BOTH=1",)
+PAIR2_BOTH_LIB = PKG_DIR / "libiqpt_pair2both.so"
+PAIR2_BOTH_STATS_LIB = PKG_DIR / "libiqpt_stats_pair2both.so"
+
+
+def build_pair_body_libs(force: bool = False) -> list[Path]:
+    """The libraries tests/test_gpu_pair_bodies.py compares (measurement and test only): the instrumented build and
+    the IQPT_PAIR2_BOTH=1 builds of the production and the instrumented library, compiled side by side."""
+    jobs = [dict(stats=True), dict(flags=PAIR2_BOTH_FLAGS, target=PAIR2_BOTH_LIB),
+            dict(stats=True, flags=PAIR2_BOTH_FLAGS, target=PAIR2_BOTH_STATS_LIB)]
+    with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
+        return list(ex.map(lambda kw: build_lib(force, **kw), jobs))
+
+
 def build_all(force: bool = False) -> None:
     build_lib(force)
     build_tools(force)
     build_oracle(force)
+    build_pair_body_libs(force)
 
 
 if __name__ == "__main__":

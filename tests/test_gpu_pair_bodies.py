@@ -1,0 +1,304 @@
+"""The two-ray kernel (kOptPipe) chooses the body of every resident pair wave-uniformly: the two-ray
+body only where ray b needs the pair (the pair is in ray b's tile mask and some lane of the wave has a ray b), the
+one-ray body on ray a alone otherwise. Every case compares accumulator bits, BGRA8, the six XORWOW words and the ray
+count with the oracle, and asserts that the launches carried kOptPipe.
+
+The crops must contain the situations that send pairs to either body. That is checked from the oracle alone, before
+the GPU result is looked at: from the oracle's per-sample ray counts (one sample at a time) the case's samples must hold
+  * a pixel with a 1-ray sample (a camera ray that ends its path: its wave runs on the tile mask) and a sample of 2 or
+    more rays (a secondary ray: its wave runs every pair, most of them for ray a alone);
+  * a pixel with a sample of 3 or more rays (a secondary ray that meets the sphere pair again).
+A sample traces at most max_depth rays, so at max_depth 1 and 2 the counts are taken at depth 8 for the same pixels
+and samples.
+
+The other forms of the kernel are other libraries (iqpt/_build.py: IQPT_PAIR2_BOTH=1 sends every pair through the
+two-ray body, the form before; libiqpt_stats.so counts the bodies). A process binds one library, so those cases run
+this file as a worker process on the library under test and compare what it wrote."""
+import ctypes as C
+import functools
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+K_OPT_PIPE = 1 << 21
+K_OPT_STATS = 1 << 7
+K_OPT_PRIO = 1 << 17
+
+W, H = 1920, 1080
+# where the left sphere faces the right one: 64 x 16 pixels, eight tiles (two- and three-scatter samples, silhouette)
+CROP_FACING = (872, 936, 624, 1, 16)
+# across the top edge of the right sphere: pixels that always miss, silhouette pixels; tiles whose masks have no sphere bit
+CROP_EDGE = (1112, 1176, 552, 1, 16)
+# a whole tiny frame: its tiles see several walls each, so the two-ray body runs beside secondary rays
+TINY = (64, 36)
+# the Cornell box plus one more triangle: 11 triangles, so the last pair (index 5) has no second triangle
+ODD_SCENE = "cornell_plus_triangle"
+
+WORKER_TIMEOUT_S = 240
+
+
+def _paths():
+    repo = Path(__file__).resolve().parent.parent
+    for p in (str(repo / "path-tracer-and-rasterizer-engine_amd"), str(repo / "oracle"), str(repo),
+              str(repo / "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+
+
+def scene_of(name):
+    """(scene, packet) of a preset, or of the odd-triangle-count scene built with the Scene API."""
+    from helpers import scene_for
+    from iqpt import Scene
+    if name != ODD_SCENE:
+        return scene_for(name)
+    sc = Scene()
+    sc.add_preset("cornell")
+    sc.add_mesh_tri("one_triangle")
+    # between the two spheres: rays that leave the big sphere towards the small one end on it (the oracle's ray counts
+    # of the facing crop change), while no camera ray of that crop sees it; a few pixels of the tiny frame do
+    sc.add_model("extra", "one_triangle", (0.5, 0.5, 1.0, 1.0), 0.0, (0.1, -0.2, -0.05))
+    return sc, sc.build_packet()
+
+
+def last_options(pt):
+    from iqpt import _lib
+    lb = _lib.load()
+    lb.iqpt_debug_last_options.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    o = C.c_int(0)
+    _lib.check(lb.iqpt_debug_last_options(pt._h, C.byref(o)), "iqpt_debug_last_options")
+    return o.value
+
+
+def render(preset, w, h, launches, depth=8, crop=None, overlap=True, stats=False):
+    """One context on the bound library: the frame after `launches`, the option set of every launch and, with
+    stats (the instrumented library), the 24 header counters of every launch."""
+    from iqpt import PathTracer, _lib, make_camera
+    from iqpt.render import pixel_set
+    _sc, pk = scene_of(preset)
+    cam = make_camera(w, h)
+    pt = PathTracer(w, h, pixels=pixel_set(w, h, *crop) if crop else None, max_depth=depth)
+    pt.set_split(_lib.SPLIT_OFF)
+    pt.set_overlap(_lib.OVERLAP_AUTO if overlap else _lib.OVERLAP_OFF)
+    pt.set_camera(cam)
+    pt.upload_packet(pk)
+    lb = _lib.load()
+    words = []
+    if stats:
+        lb.iqpt_debug_set_kernel_options.argtypes = [C.c_void_p, C.c_int]
+        lb.iqpt_debug_default_options.restype = C.c_int
+        lb.iqpt_debug_read_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        opt = lb.iqpt_debug_default_options() | K_OPT_PRIO | K_OPT_STATS | K_OPT_PIPE
+        _lib.check(lb.iqpt_debug_set_kernel_options(pt._h, opt), "iqpt_debug_set_kernel_options")
+    opts = []
+    for s in launches:
+        pt.render(s)
+        opts.append(last_options(pt))
+        if stats:
+            pt.sync()
+            buf = (C.c_ulonglong * 24)()
+            _lib.check(lb.iqpt_debug_read_stats(pt._h, buf), "iqpt_debug_read_stats")   # reads and clears
+            words.append([int(v) for v in buf])
+    pt.sync()
+    lin, bgra = pt.read()
+    out = (lin, bgra, pt.read_rng(), pt.rays())
+    pt.close()
+    return out, opts, words
+
+
+# ---- worker process: the same render on another library, results to an .npz ----
+def worker_main(argv):
+    lib, out_path, cases = argv[0], argv[1], json.loads(argv[2])
+    _paths()
+    from iqpt import _lib
+    _lib.LIB_PATH = Path(lib).resolve()
+    res = {}
+    for i, c in enumerate(cases):
+        (lin, bgra, rng, rays), opts, words = render(c["preset"], c["w"], c["h"], c["launches"], depth=c["depth"],
+                                                     crop=tuple(c["crop"]) if c["crop"] else None,
+                                                     overlap=c["overlap"], stats=c["stats"])
+        res[f"lin{i}"], res[f"bgra{i}"], res[f"rng{i}"] = lin, bgra, rng
+        res[f"rays{i}"] = np.array([rays], dtype=np.uint64)
+        res[f"opts{i}"] = np.array(opts, dtype=np.int64)
+        res[f"words{i}"] = np.array(words, dtype=np.uint64).reshape(len(words), 24)
+    np.savez(out_path, **res)
+
+
+if __name__ == "__main__":
+    worker_main(sys.argv[1:])
+    sys.exit(0)
+
+
+pytestmark = pytest.mark.gpu
+
+
+def case(preset, w, h, launches, depth=8, crop=None, overlap=True, stats=False):
+    return {"preset": preset, "w": w, "h": h, "launches": list(launches), "depth": depth,
+            "crop": list(crop) if crop else None, "overlap": overlap, "stats": stats}
+
+
+def run_on(lib, cases, tmp_path):
+    """The cases in one worker process bound to `lib`: a list of ((lin, bgra, rng, rays), opts, words)."""
+    out = tmp_path / (Path(lib).stem + ".npz")
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [__file__, str(lib), str(out), json.dumps(cases)]
+    proc = subprocess.run(cmd, capture_output=True, text=True, timeout=WORKER_TIMEOUT_S)
+    assert proc.returncode == 0, f"worker on {lib} ended with {proc.returncode}\n{proc.stdout}\n{proc.stderr}"
+    z = np.load(out)
+    return [((z[f"lin{i}"], z[f"bgra{i}"], z[f"rng{i}"], int(z[f"rays{i}"][0])), z[f"opts{i}"].tolist(),
+             z[f"words{i}"].astype(np.uint64)) for i in range(len(cases))]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_steps(preset, w, h, crop, total, depth):
+    """The oracle frame after `total` samples, rendered one sample at a time (consecutive reference launches, so
+    the same frame as any grouping into launches), and the rays of every sample and pixel, [total, npix]. Computed
+    once per (frame, samples, depth) and shared; the tests do not change it."""
+    import oracle
+    from iqpt import make_camera
+    from iqpt.render import pixel_set
+    _sc, pk = scene_of(preset)
+    fr = oracle.OracleFrame(w, h, pixels=pixel_set(w, h, *crop) if crop else None, max_depth=depth)
+    cam = make_camera(w, h)
+    per_sample = np.zeros((total, fr.npix), dtype=np.int64)
+    for k in range(total):
+        before = fr.rays.copy()
+        fr.render(pk, cam, 1)
+        per_sample[k] = (fr.rays - before).astype(np.int64)
+    per_sample.setflags(write=False)
+    return fr, per_sample
+
+
+def check_inputs(preset, w, h, crop, total, depth, twice=True):
+    """The condition on the inputs (module docstring), from the oracle alone."""
+    _, c = oracle_steps(preset, w, h, crop, total, depth if depth >= 3 else 8)
+    ends_and_scatters = int(((c == 1).any(axis=0) & (c >= 2).any(axis=0)).sum())
+    scatters_twice = int((c >= 3).any(axis=0).sum())
+    print(f"{preset} {crop} {total} samples depth {depth}: {ends_and_scatters} pixels with a 1-ray and a >= 2-ray "
+          f"sample, {scatters_twice} with a >= 3-ray sample")
+    assert ends_and_scatters >= 1
+    assert scatters_twice >= 1 or not twice
+
+
+def same_as_oracle(out, fr):
+    lin, bgra, rng, rays = out
+    a, b = lin[:, :3], fr.lin[:, :3]
+    both_nan = np.isnan(a) & np.isnan(b)
+    assert np.all((a.view(np.uint32) == b.view(np.uint32)) | both_nan)
+    assert np.array_equal(bgra, fr.bgra)
+    assert np.array_equal(rng, fr.states)
+    assert rays == int(fr.rays.sum())
+
+
+def same(a, b):
+    assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
+    assert np.array_equal(a[1], b[1])
+    assert np.array_equal(a[2], b[2])
+    assert a[3] == b[3]
+
+
+def check_case(preset, w, h, launches, depth=8, crop=None, overlap=True, twice=True):
+    check_inputs(preset, w, h, crop, sum(launches), depth, twice)
+    out, opts, _ = render(preset, w, h, launches, depth=depth, crop=crop, overlap=overlap)
+    assert all(o & K_OPT_PIPE for o in opts), [hex(o) for o in opts]
+    same_as_oracle(out, oracle_steps(preset, w, h, crop, sum(launches), depth)[0])
+    return out, opts
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+def test_steady_state(require_gpu, overlap):
+    """The facing crop, launches of 1, 2, 5 and 64 samples: waves whose ray a is a secondary ray (every pair, most of
+    them in the one-ray body) beside ray b's tile-mask pairs in the two-ray body."""
+    check_case("cornell", W, H, [1, 2, 5, 64], crop=CROP_FACING, overlap=overlap)
+
+
+@pytest.mark.parametrize("launches", [[1, 1, 1], [2]])
+def test_no_ray_b_in_the_wave(require_gpu, launches):
+    """A launch's last sample has no ray b: every pair of those iterations takes the one-ray body (all of a 1-spp
+    launch, the interactive cadence)."""
+    check_case("cornell", W, H, launches, crop=CROP_FACING)
+
+
+def test_silhouette(require_gpu):
+    """A crop across a sphere's outer edge: tiles whose masks have no sphere bit, so the sphere pair runs for ray a
+    alone (test_sphere_pair) when a secondary ray is in the wave."""
+    check_case("cornell", W, H, [3, 4], crop=CROP_EDGE)
+
+
+def test_every_pair_in_ray_b_mask(require_gpu):
+    """A whole 64 x 36 Cornell frame: each tile sees several walls, so the two-ray body runs beside secondary rays."""
+    check_case("cornell", TINY[0], TINY[1], [3, 4])
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3, 16])
+def test_depths(require_gpu, depth):
+    """max_depth 1 (no secondary ray is traced: tile masks only), 2, 3 and 16 (the MAXD-16 variant)."""
+    check_case("cornell", W, H, [5, 7], depth=depth, crop=CROP_FACING)
+
+
+@pytest.mark.parametrize("preset,size,depth", [("app_default", (317, 181), 5), ("c1_plumbing", (250, 250), 2)])
+def test_ragged_frames(require_gpu, preset, size, depth):
+    """Ragged frames, partial tiles and partial waves (act_a false on some lanes of a one-ray body). The C1 scene has
+    a single sphere, and a ray that leaves a sphere cannot meet the same one again, so no path of it scatters twice:
+    only the first input condition is asked of it."""
+    check_case(preset, size[0], size[1], [3, 4], depth=depth, twice=preset != "c1_plumbing")
+
+
+@pytest.mark.parametrize("frame", ["crop", "tiny"])
+def test_odd_triangle_count(require_gpu, frame):
+    """11 triangles: the last pair has one triangle (`second` false). On the facing crop no tile sees the extra
+    triangle, so the tail pair runs in the one-ray body whenever a secondary ray is in the wave; on the tiny frame
+    it is in some tiles' masks too (two-ray body)."""
+    from iqpt.scene import packet_stats
+    _sc, pk = scene_of(ODD_SCENE)
+    assert packet_stats(pk)["triangles"] % 2 == 1, packet_stats(pk)
+    w, h, crop = (W, H, CROP_FACING) if frame == "crop" else (TINY[0], TINY[1], None)
+    # from the oracle alone: rays of these pixels' paths end on the extra triangle (the ray count differs from the box's)
+    assert int(oracle_steps(ODD_SCENE, w, h, crop, 7, 8)[0].rays.sum()) != int(oracle_steps("cornell", w, h, crop, 7, 8)[0].rays.sum())
+    check_case(ODD_SCENE, w, h, [3, 4], crop=crop)
+
+
+def test_forms_agree(require_gpu, tmp_path):
+    """IQPT_PAIR2_BOTH=1 (every pair through the two-ray body, the form before) gives the default library's output
+    bit for bit, and both give the oracle's."""
+    from iqpt import _build
+    lib = _build.build_lib(flags=_build.PAIR2_BOTH_FLAGS, target=_build.PAIR2_BOTH_LIB)
+    cases = [case("cornell", W, H, [1, 2, 5, 64], crop=CROP_FACING), case("cornell", W, H, [3, 4], crop=CROP_EDGE),
+             case("cornell", TINY[0], TINY[1], [3, 4]), case(ODD_SCENE, W, H, [3, 4], crop=CROP_FACING),
+             case("app_default", 317, 181, [3, 4], depth=5)]
+    both = run_on(lib, cases, tmp_path)
+    for c, (out_b, opts_b, _) in zip(cases, both):
+        crop = tuple(c["crop"]) if c["crop"] else None
+        out, opts = check_case(c["preset"], c["w"], c["h"], c["launches"], depth=c["depth"], crop=crop)
+        assert all(o & K_OPT_PIPE for o in opts_b), [hex(o) for o in opts_b]
+        same(out, out_b)
+
+
+def test_stats_build_counts_the_bodies(require_gpu, tmp_path):
+    """libiqpt_stats.so: header word 8 counts the triangle pairs the waves visited, word 23 those that ran the one-ray
+    body. 1-spp launches have no ray b, so no two-ray body runs (word 23 == word 8); a 64-spp launch of the facing
+    crop runs both bodies (0 < word 23 < word 8). The primitive tests executed (words 20, 21: needed tests only) are
+    those of the form before, whose word 23 is 0."""
+    from iqpt import _build
+    new_lib = _build.build_lib(stats=True)
+    old_lib = _build.build_lib(stats=True, flags=_build.PAIR2_BOTH_FLAGS, target=_build.PAIR2_BOTH_STATS_LIB)
+    cases = [case("cornell", W, H, [1, 1, 1], crop=CROP_FACING, overlap=False, stats=True),
+             case("cornell", W, H, [64], crop=CROP_FACING, overlap=False, stats=True)]
+    new, old = run_on(new_lib, cases, tmp_path), run_on(old_lib, cases, tmp_path)
+    for c, (out_n, opts_n, w_n), (out_o, opts_o, w_o) in zip(cases, new, old):
+        assert all(o & K_OPT_PIPE and o & K_OPT_STATS for o in opts_n + opts_o), [hex(o) for o in opts_n + opts_o]
+        same_as_oracle(out_n, oracle_steps(c["preset"], c["w"], c["h"], tuple(c["crop"]), sum(c["launches"]),
+                                           c["depth"])[0])
+        same(out_n, out_o)
+        print(c["launches"], "words 8 / 23 new", w_n[:, 8].tolist(), w_n[:, 23].tolist(), "old", w_o[:, 8].tolist(),
+              w_o[:, 23].tolist(), "tests", w_n[:, 20:22].tolist())
+        assert np.array_equal(w_n[:, 8], w_o[:, 8]) and np.array_equal(w_n[:, 9], w_o[:, 9])
+        assert np.array_equal(w_n[:, 20:22], w_o[:, 20:22])
+        assert np.all(w_o[:, 23] == 0)
+        assert np.all(w_n[:, 8] > 0)
+        if c["launches"] == [64]:
+            assert np.all((0 < w_n[:, 23]) & (w_n[:, 23] < w_n[:, 8]))
+        else:
+            assert np.array_equal(w_n[:, 23], w_n[:, 8])

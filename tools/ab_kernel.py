@@ -175,6 +175,10 @@ def main():
                  "active_lane_frac": active / max(1, it * 64), "scatter_exec_per_iter": sc_ex / max(1, it),
                  # two-ray kernel: iterations whose scatter served ray a's hits and promoted ray b's together
                  "scatter_both_per_iter": s[22] / max(1, it),
+                 # two-ray kernel: of the triangle pairs visited (word 8), those that ran the one-ray body (word 23: ray b
+                 # did not need the pair) and the two-ray body
+                 "tri_pair_one_ray_bodies_per_iter": s[23] / max(1, it),
+                 "tri_pair_two_ray_bodies_per_iter": (tri_tests - s[23]) / max(1, it),
                  "scatter_lanes_per_exec": sc_l / max(1, sc_ex), "term_exec_per_iter": t_ex / max(1, it),
                  "term_lanes_per_exec": t_l / max(1, t_ex), "rays": pt.rays(),
                  "tri_pair_tests_per_iter": tri_tests / max(1, it), "sph_pair_tests_per_iter": sph_tests / max(1, it),

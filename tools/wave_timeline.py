@@ -110,6 +110,10 @@ res = {"config": args.config, "spp": spp, "two_ray": args.two_ray, "overlap": ar
        "scatter_iteration_frac": round(v[3] / max(v[0], 1), 3),
        # two-ray kernel: iterations whose one scatter served ray a's sphere hits and promoted ray b's together
        "scatter_both_iteration_frac": round(v[22] / max(v[0], 1), 3), "scatter_lanes_per_scatter_iteration": round(v[4] / max(v[3], 1), 2),
+       # two-ray kernel: triangle pairs visited (word 8) and those that ran the one-ray body (word 23: ray b did not
+       # need the pair); the rest ran the two-ray body
+       "tri_pairs_visited": v[8], "tri_pair_one_ray_bodies": v[23], "tri_pair_two_ray_bodies": v[8] - v[23],
+       "one_ray_body_frac": round(v[23] / max(v[8], 1), 3),
        "end_iteration_frac": round(v[5] / max(v[0], 1), 3), "end_lanes_per_end_iteration": round(v[6] / max(v[5], 1), 2),
        "full_loop_iteration_frac": round(v[10] / max(v[0], 1), 3),
        "iters_per_wave": pct(iters[busy]), "wave_us": pct(dur[busy]), "us_per_iter": pct(us_iter),

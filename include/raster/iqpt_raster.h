@@ -92,6 +92,30 @@ int iqpt_raster_stage_time(iqpt_raster* r, double stage_ms[5]);
 /* Work of the last draw: [0] triangles submitted, [1] set-up records, [2] (tile, triangle) pairs. */
 int iqpt_raster_stats(iqpt_raster* r, uint64_t counts[3]);
 
+/* ---------------------------------------------------------------- G-buffer
+ * What a denoiser needs of the uploaded scene through the current camera, per pixel and noise-free: the pipeline
+ * with ONE sample per pixel (whatever `samples` is) over an index list in which every triangle appears with both
+ * windings, so that surfaces seen from behind have a guide too (the path tracer's triangle test is two-sided).
+ * Per pixel, for the piece that owns the centre after the depth test:
+ *   normal_z: 4 floats, the interpolated world normal normalised (not flipped towards the viewer; 0, 0, 0 where
+ *             nothing was drawn) and the D32 depth (1.0 where nothing was drawn);
+ *   id:       the draw index (the model's position in iqpt_scene_draw_list), IQPT_RASTER_NO_PRIM where nothing
+ *             was drawn.
+ * Both are compact row-major, width*height entries. A draw's frame does not depend on G-buffer passes before or
+ * after it, and iqpt_raster_read keeps returning the last draw. */
+/* Enqueues the pass on the rasterizer's stream (it waits once for two counters, as a draw does). The result is
+ * kept until the camera or the scene changes: a second call in between does nothing. */
+int iqpt_raster_gbuffer(iqpt_raster* r);
+/* Synchronises and copies the G-buffer out. Either pointer may be NULL. IQPT_ERR_NOT_READY without a G-buffer
+ * of the current camera and scene. */
+int iqpt_raster_read_gbuffer(iqpt_raster* r, float* normal_z, uint32_t* id);
+/* Synchronises and returns the device buffers; they stay valid until the next iqpt_raster_gbuffer,
+ * iqpt_raster_upload_scene, iqpt_raster_set_camera or iqpt_raster_destroy. */
+int iqpt_raster_gbuffer_device(iqpt_raster* r, const void** normal_z_device, const void** id_device);
+/* Sum of the passes' durations (HIP events, vertex stage to tile kernel) and their count since the last call
+ * (then cleared). Synchronises. */
+int iqpt_raster_gbuffer_time(iqpt_raster* r, double* total_ms, uint64_t* passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,15 @@ struct geometry {
     }
 };
 
+// what a tile kernel consumes: the set-up records, the sorted (tile, record) pairs ([1] after the sort) and the
+// tiles' ranges. A draw and a G-buffer pass each keep their own, so neither disturbs the other's.
+struct lists {
+    dbuf recs, keys[2], vals[2], ranges;
+    void release() {
+        for (dbuf* b : {&recs, &keys[0], &keys[1], &vals[0], &vals[1], &ranges}) b->release();
+    }
+};
+
 constexpr int kEvents = 6;
 
 }  // namespace
@@ -67,8 +76,15 @@ struct iqpt_raster {
     bool have_camera = false, have_scene = false, have_frame = false;
     dbuf camera;                  // view[16], projection[16]
     geometry scene, direct;       // the uploaded scene; the vertices of the last draw_clip
-    dbuf recs, cnt, frame, depth_samples, prim_samples, sort_temp;
-    dbuf keys[2], vals[2], ranges;
+    dbuf cnt, frame, depth_samples, prim_samples, sort_temp;
+    lists draw_lists;             // of the last draw (iqpt_raster_read re-runs its tile kernel over them)
+    lists guide_lists;            // of the G-buffer pass
+    dbuf guide_nz, guide_id;      // the G-buffer: float4 (n, z) and the draw index per pixel
+    bool have_gbuffer = false;    // guide_* hold the uploaded scene through the current camera
+    hipEvent_t guide_ev[2] = {};
+    bool guide_pending = false;
+    double guide_ms = 0.0;
+    uint64_t guide_passes = 0;
     iqr::counters* host_cnt = nullptr;    // pinned
     uint32_t last_nrec = 0, last_npairs = 0, last_ntris = 0;
     hipEvent_t ev[kEvents] = {};
@@ -99,9 +115,83 @@ int collect(iqpt_raster* r) {
     return IQPT_OK;
 }
 
+// the same for the last G-buffer pass
+int collect_guide(iqpt_raster* r) {
+    if (!r->guide_pending) return IQPT_OK;
+    IQR_HIP(hipEventSynchronize(r->guide_ev[1]));
+    float ms = 0.0f;
+    IQR_HIP(hipEventElapsedTime(&ms, r->guide_ev[0], r->guide_ev[1]));
+    r->guide_ms += ms;
+    r->guide_pending = false;
+    return IQPT_OK;
+}
+
 int upload(dbuf& b, const void* src, size_t bytes, hipStream_t s) {
     IQR_HIP(b.reserve(std::max<size_t>(bytes, 16)));
     if (bytes) IQR_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    return IQPT_OK;
+}
+
+// Setup, binning, sort and tile ranges of geometry g into the lists l, on the rasterizer's stream. guide: the
+// G-buffer's doubled index list, whose submission indices run to 2 ntris. ev (may be NULL): two
+// events, recorded after the setup and after the binning.
+int build_lists(iqpt_raster* r, geometry& g, const iqr::frame_params& fp, bool guide, lists& l, hipEvent_t* ev,
+                uint32_t& nrec, uint32_t& npairs) {
+    hipStream_t s = r->stream;
+    const uint32_t nsub = guide ? 2 * g.ntris : g.ntris;
+    // setup: records and pair positions are claimed with two counters; a record buffer that proves too small
+    // is grown to the count the pass reported and the pass is redone (never a silent limit)
+    nrec = npairs = 0;
+    if (g.ntris) {
+        size_t cap = std::max<size_t>(l.recs.bytes / sizeof(iqr::setup_rec), 1024);
+        for (int attempt = 0;; ++attempt) {
+            IQR_HIP(l.recs.reserve(cap * sizeof(iqr::setup_rec)));
+            IQR_HIP(hipMemsetAsync(r->cnt.p, 0, sizeof(iqr::counters), s));
+            IQR_HIP((guide ? iqr::launch_setup_guide : iqr::launch_setup)(
+                s, fp, g.draws.as<iqr::draw_rec>(), g.ndraws, g.tend.as<uint32_t>(), g.ntris, g.indices.as<uint32_t>(),
+                g.clip.as<float>(), g.wn.as<float>(), l.recs.as<iqr::setup_rec>(),
+                (uint32_t)std::min<size_t>(cap, 0xffffffffu), r->cnt.as<iqr::counters>()));
+            IQR_HIP(hipMemcpyAsync(r->host_cnt, r->cnt.p, sizeof(iqr::counters), hipMemcpyDeviceToHost, s));
+            IQR_HIP(hipStreamSynchronize(s));
+            if (r->host_cnt->npairs >= 0xffffffffull || r->host_cnt->nrec >= 0xffffffffull)
+                return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^32 (tile, triangle) pairs in one frame");
+            if (r->host_cnt->nrec <= cap) break;
+            if (attempt) return iqpt::fail(IQPT_ERR_HIP, "setup record count changed between passes");
+            cap = (size_t)r->host_cnt->nrec;
+        }
+        nrec = (uint32_t)r->host_cnt->nrec;
+        npairs = (uint32_t)r->host_cnt->npairs;
+    }
+    if (ev) IQR_HIP(hipEventRecord(ev[0], s));
+
+    const int in = 0, out = 1;
+    // sort key: tile << key_bits | (submission index << 3 | piece), key_bits just wide enough for this draw
+    unsigned key_bits = iqr::kPieceBits + 1;
+    while ((1ull << key_bits) < ((unsigned long long)nsub << iqr::kPieceBits)) ++key_bits;
+    if (npairs) {
+        for (int k = 0; k < 2; ++k) {
+            IQR_HIP(l.keys[k].reserve((size_t)npairs * sizeof(unsigned long long)));
+            IQR_HIP(l.vals[k].reserve((size_t)npairs * sizeof(uint32_t)));
+        }
+        IQR_HIP(iqr::launch_bin(s, fp, l.recs.as<iqr::setup_rec>(), nrec, key_bits, l.keys[in].as<unsigned long long>(),
+                                l.vals[in].as<uint32_t>()));
+    }
+    if (ev) IQR_HIP(hipEventRecord(ev[1], s));
+    if (npairs) {
+        unsigned tile_bits = 1;
+        while ((1ull << tile_bits) < (unsigned long long)fp.ntx * fp.nty) ++tile_bits;
+        const unsigned end_bit = key_bits + tile_bits;
+        size_t need = 0;
+        IQR_HIP(iqr::sort_pairs(s, nullptr, need, l.keys[in].as<unsigned long long>(),
+                                l.keys[out].as<unsigned long long>(), l.vals[in].as<uint32_t>(),
+                                l.vals[out].as<uint32_t>(), npairs, end_bit));
+        IQR_HIP(r->sort_temp.reserve(std::max<size_t>(need, 16)));
+        need = r->sort_temp.bytes;
+        IQR_HIP(iqr::sort_pairs(s, r->sort_temp.p, need, l.keys[in].as<unsigned long long>(),
+                                l.keys[out].as<unsigned long long>(), l.vals[in].as<uint32_t>(),
+                                l.vals[out].as<uint32_t>(), npairs, end_bit));
+    }
+    IQR_HIP(iqr::launch_ranges(s, fp, l.keys[out].as<unsigned long long>(), npairs, key_bits, l.ranges.as<uint32_t>()));
     return IQPT_OK;
 }
 
@@ -119,61 +209,11 @@ int run_draw(iqpt_raster* r, geometry& g, bool vertex_stage) {
     }
     IQR_HIP(hipEventRecord(r->ev[1], s));
 
-    // setup: records and pair positions are claimed with two counters; a record buffer that proves too small
-    // is grown to the count the pass reported and the pass is redone (never a silent limit)
     uint32_t nrec = 0, npairs = 0;
-    if (g.ntris) {
-        size_t cap = std::max<size_t>(r->recs.bytes / sizeof(iqr::setup_rec), 1024);
-        for (int attempt = 0;; ++attempt) {
-            IQR_HIP(r->recs.reserve(cap * sizeof(iqr::setup_rec)));
-            IQR_HIP(hipMemsetAsync(r->cnt.p, 0, sizeof(iqr::counters), s));
-            IQR_HIP(iqr::launch_setup(s, fp, g.draws.as<iqr::draw_rec>(), g.ndraws, g.tend.as<uint32_t>(), g.ntris,
-                                      g.indices.as<uint32_t>(), g.clip.as<float>(), g.wn.as<float>(),
-                                      r->recs.as<iqr::setup_rec>(), (uint32_t)std::min<size_t>(cap, 0xffffffffu),
-                                      r->cnt.as<iqr::counters>()));
-            IQR_HIP(hipMemcpyAsync(r->host_cnt, r->cnt.p, sizeof(iqr::counters), hipMemcpyDeviceToHost, s));
-            IQR_HIP(hipStreamSynchronize(s));
-            if (r->host_cnt->npairs >= 0xffffffffull || r->host_cnt->nrec >= 0xffffffffull)
-                return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^32 (tile, triangle) pairs in one frame");
-            if (r->host_cnt->nrec <= cap) break;
-            if (attempt) return iqpt::fail(IQPT_ERR_HIP, "setup record count changed between passes");
-            cap = (size_t)r->host_cnt->nrec;
-        }
-        nrec = (uint32_t)r->host_cnt->nrec;
-        npairs = (uint32_t)r->host_cnt->npairs;
-    }
-    IQR_HIP(hipEventRecord(r->ev[2], s));
-
-    const int in = 0, out = 1;
-    // sort key: tile << key_bits | (submission index << 3 | piece), key_bits just wide enough for this draw
-    unsigned key_bits = iqr::kPieceBits + 1;
-    while ((1ull << key_bits) < ((unsigned long long)g.ntris << iqr::kPieceBits)) ++key_bits;
-    if (npairs) {
-        for (int k = 0; k < 2; ++k) {
-            IQR_HIP(r->keys[k].reserve((size_t)npairs * sizeof(unsigned long long)));
-            IQR_HIP(r->vals[k].reserve((size_t)npairs * sizeof(uint32_t)));
-        }
-        IQR_HIP(iqr::launch_bin(s, fp, r->recs.as<iqr::setup_rec>(), nrec, key_bits, r->keys[in].as<unsigned long long>(),
-                                r->vals[in].as<uint32_t>()));
-    }
-    IQR_HIP(hipEventRecord(r->ev[3], s));
-    if (npairs) {
-        unsigned tile_bits = 1;
-        while ((1ull << tile_bits) < (unsigned long long)fp.ntx * fp.nty) ++tile_bits;
-        const unsigned end_bit = key_bits + tile_bits;
-        size_t need = 0;
-        IQR_HIP(iqr::sort_pairs(s, nullptr, need, r->keys[in].as<unsigned long long>(),
-                                r->keys[out].as<unsigned long long>(), r->vals[in].as<uint32_t>(),
-                                r->vals[out].as<uint32_t>(), npairs, end_bit));
-        IQR_HIP(r->sort_temp.reserve(std::max<size_t>(need, 16)));
-        need = r->sort_temp.bytes;
-        IQR_HIP(iqr::sort_pairs(s, r->sort_temp.p, need, r->keys[in].as<unsigned long long>(),
-                                r->keys[out].as<unsigned long long>(), r->vals[in].as<uint32_t>(),
-                                r->vals[out].as<uint32_t>(), npairs, end_bit));
-    }
-    IQR_HIP(iqr::launch_ranges(s, fp, r->keys[out].as<unsigned long long>(), npairs, key_bits, r->ranges.as<uint32_t>()));
+    if (int st = build_lists(r, g, fp, false, r->draw_lists, r->ev + 2, nrec, npairs)) return st;
     IQR_HIP(hipEventRecord(r->ev[4], s));
-    IQR_HIP(iqr::launch_tiles(s, fp, r->recs.as<iqr::setup_rec>(), r->vals[out].as<uint32_t>(), r->ranges.as<uint32_t>(),
+    const lists& l = r->draw_lists;
+    IQR_HIP(iqr::launch_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
                               r->frame.as<uint32_t>(), nullptr, nullptr));
     IQR_HIP(hipEventRecord(r->ev[5], s));
     r->pending = true;
@@ -221,7 +261,10 @@ int iqpt_raster_create(int device, uint32_t width, uint32_t height, uint32_t sam
     if ((e = r->cnt.reserve(sizeof(iqr::counters))) != hipSuccess) return fail_with(e, "hipMalloc(counters)");
     if ((e = r->camera.reserve(32 * sizeof(float))) != hipSuccess) return fail_with(e, "hipMalloc(camera)");
     if ((e = r->frame.reserve((size_t)width * height * 4)) != hipSuccess) return fail_with(e, "hipMalloc(frame)");
-    if ((e = r->ranges.reserve((size_t)r->fp.ntx * r->fp.nty * 8)) != hipSuccess) return fail_with(e, "hipMalloc(ranges)");
+    for (lists* l : {&r->draw_lists, &r->guide_lists})
+        if ((e = l->ranges.reserve((size_t)r->fp.ntx * r->fp.nty * 8)) != hipSuccess) return fail_with(e, "hipMalloc(ranges)");
+    for (hipEvent_t& ev : r->guide_ev)
+        if ((e = hipEventCreate(&ev)) != hipSuccess) return fail_with(e, "hipEventCreate");
     *out = r;
     return IQPT_OK;
 }
@@ -232,9 +275,13 @@ int iqpt_raster_destroy(iqpt_raster* r) {
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     r->scene.release();
     r->direct.release();
-    for (dbuf* b : {&r->camera, &r->recs, &r->cnt, &r->frame, &r->depth_samples, &r->prim_samples, &r->sort_temp,
-                    &r->keys[0], &r->keys[1], &r->vals[0], &r->vals[1], &r->ranges})
+    r->draw_lists.release();
+    r->guide_lists.release();
+    for (dbuf* b : {&r->camera, &r->cnt, &r->frame, &r->depth_samples, &r->prim_samples, &r->sort_temp, &r->guide_nz,
+                    &r->guide_id})
         b->release();
+    for (hipEvent_t ev : r->guide_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (r->host_cnt) (void)hipHostFree(r->host_cnt);
     for (hipEvent_t ev : r->ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -256,6 +303,7 @@ int iqpt_raster_set_camera(iqpt_raster* r, const iqpt_camera* cam) {
     IQR_HIP(hipStreamSynchronize(r->stream));
     r->have_camera = true;
     r->scene.transformed = false;
+    r->have_gbuffer = false;
     return IQPT_OK;
 }
 
@@ -301,6 +349,7 @@ int iqpt_raster_upload_scene(iqpt_raster* r, const iqpt_scene* scene) {
         d.src_vbase = found->vbase;
         d.ibase = found->ibase;
         d.tbase = (uint32_t)ntris;
+        d.item = i;
         nverts += it.num_vertices;
         ntris += it.num_indices / 3;
         if (ntris >= iqr::kMaxTriangles || nverts >= 0x7fffffffu)
@@ -327,6 +376,7 @@ int iqpt_raster_upload_scene(iqpt_raster* r, const iqpt_scene* scene) {
     g.ntris = (uint32_t)ntris;
     g.transformed = false;
     r->have_scene = true;
+    r->have_gbuffer = false;
     return IQPT_OK;
 }
 
@@ -379,8 +429,9 @@ int iqpt_raster_read(iqpt_raster* r, uint8_t* bgra, float* depth_samples, uint32
         // the tile kernel of the last draw again, over the same sorted lists, with the per-sample outputs on
         IQR_HIP(r->depth_samples.reserve(nsamp * 4));
         IQR_HIP(r->prim_samples.reserve(nsamp * 4));
-        IQR_HIP(iqr::launch_tiles(s, r->fp, r->recs.as<iqr::setup_rec>(), r->vals[1].as<uint32_t>(),
-                                  r->ranges.as<uint32_t>(), r->frame.as<uint32_t>(), r->depth_samples.as<float>(),
+        const lists& l = r->draw_lists;
+        IQR_HIP(iqr::launch_tiles(s, r->fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(),
+                                  l.ranges.as<uint32_t>(), r->frame.as<uint32_t>(), r->depth_samples.as<float>(),
                                   r->prim_samples.as<uint32_t>()));
         if (depth_samples) IQR_HIP(hipMemcpyAsync(depth_samples, r->depth_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
         if (prim_samples) IQR_HIP(hipMemcpyAsync(prim_samples, r->prim_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
@@ -435,4 +486,76 @@ int iqpt_raster_stats(iqpt_raster* r, uint64_t counts[3]) {
     return IQPT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- G-buffer
+int iqpt_raster_gbuffer(iqpt_raster* r) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if (!r->have_camera || !r->have_scene) return iqpt::fail(IQPT_ERR_NOT_READY, "gbuffer before set_camera / upload_scene");
+    if (r->have_gbuffer) return IQPT_OK;       // kept until the camera or the scene changes
+    geometry& g = r->scene;
+    if (2ull * g.ntris >= iqr::kMaxTriangles)
+        return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^27 triangles in a G-buffer pass (every one is submitted twice)");
+    if (int st = set_device(r)) return st;
+    if (int st = collect_guide(r)) return st;
+    hipStream_t s = r->stream;
+    const size_t npix = (size_t)r->fp.width * r->fp.height;
+    IQR_HIP(r->guide_nz.reserve(npix * 16));
+    IQR_HIP(r->guide_id.reserve(npix * 4));
+    iqr::frame_params fp = r->fp;
+    fp.samples = 1;                            // one sample per pixel, whatever the rasterizer's own count
+    IQR_HIP(hipEventRecord(r->guide_ev[0], s));
+    if (!g.transformed) {
+        IQR_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
+                                   g.mesh_verts.as<float>(), r->camera.as<float>(), r->camera.as<float>() + 16,
+                                   g.clip.as<float>(), g.wn.as<float>()));
+        g.transformed = true;
+    }
+    uint32_t nrec = 0, npairs = 0;
+    lists& l = r->guide_lists;
+    if (int st = build_lists(r, g, fp, true, l, nullptr, nrec, npairs)) return st;
+    IQR_HIP(iqr::launch_guide_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
+                                    r->guide_nz.p, r->guide_id.as<uint32_t>()));
+    IQR_HIP(hipEventRecord(r->guide_ev[1], s));
+    r->guide_pending = true;
+    r->guide_passes += 1;
+    r->have_gbuffer = true;
+    return IQPT_OK;
+}
+
+int iqpt_raster_read_gbuffer(iqpt_raster* r, float* normal_z, uint32_t* id) {
+    if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
+    if (!r->have_gbuffer) return iqpt::fail(IQPT_ERR_NOT_READY, "read_gbuffer without a G-buffer of the current camera and scene");
+    if (int st = set_device(r)) return st;
+    const size_t npix = (size_t)r->fp.width * r->fp.height;
+    if (normal_z) IQR_HIP(hipMemcpyAsync(normal_z, r->guide_nz.p, npix * 16, hipMemcpyDeviceToHost, r->stream));
+    if (id) IQR_HIP(hipMemcpyAsync(id, r->guide_id.p, npix * 4, hipMemcpyDeviceToHost, r->stream));
+    IQR_HIP(hipStreamSynchronize(r->stream));
+    return IQPT_OK;
+}
+
+int iqpt_raster_gbuffer_device(iqpt_raster* r, const void** normal_z, const void** id) {
+    if (!r || !normal_z || !id) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (!r->have_gbuffer) return iqpt::fail(IQPT_ERR_NOT_READY, "gbuffer_device without a G-buffer of the current camera and scene");
+    if (int st = set_device(r)) return st;
+    IQR_HIP(hipStreamSynchronize(r->stream));  // the caller reads them on a stream of its own
+    *normal_z = r->guide_nz.p;
+    *id = r->guide_id.p;
+    return IQPT_OK;
+}
+
+int iqpt_raster_gbuffer_time(iqpt_raster* r, double* total_ms, uint64_t* passes) {
+    if (!r || !total_ms || !passes) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (int st = set_device(r)) return st;
+    if (int st = collect_guide(r)) return st;
+    *total_ms = r->guide_ms;
+    *passes = r->guide_passes;
+    r->guide_ms = 0.0;
+    r->guide_passes = 0;
+    return IQPT_OK;
+}
+
 }  // extern "C"
+
+void iqr::frame_size(const iqpt_raster* r, uint32_t* width, uint32_t* height) {
+    *width = r->fp.width;
+    *height = r->fp.height;
+}

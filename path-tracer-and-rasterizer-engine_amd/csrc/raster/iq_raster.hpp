@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+struct iqpt_raster;
+
 namespace iqr {
 
 constexpr int kTile = 8;                       // 8 x 8 pixels: one wave64 per tile, lane = pixel
@@ -27,6 +29,7 @@ struct draw_rec {
     uint32_t src_vbase;     // first vertex of its mesh in the mesh vertex pool
     uint32_t ibase;         // first index of its mesh in the index pool
     uint32_t tbase;         // submission index of its first triangle
+    uint32_t item;          // the draw index: its model's position in iqpt_scene_draw_list (setup_rec.pad[0])
 };
 
 // Set-up triangle, 32 words, read wave-uniformly by the tile kernel.
@@ -39,7 +42,7 @@ struct setup_rec {
     uint32_t key;                     // submission index << kPieceBits | piece
     uint32_t tile_x0y0, tile_x1y1;    // inclusive tile bounding box, x | y << 16
     uint32_t pair_base;               // first of its (tile, key) pairs
-    uint32_t pad[4];
+    uint32_t pad[4];                  // pad[0]: the draw index (draw_rec.item), what the G-buffer's id plane holds
 };
 static_assert(sizeof(setup_rec) == 128, "setup record is 32 words");
 
@@ -60,6 +63,11 @@ hipError_t launch_vertex(hipStream_t s, const draw_rec* draws, uint32_t ndraws, 
 hipError_t launch_setup(hipStream_t s, const frame_params& fp, const draw_rec* draws, uint32_t ndraws,
                         const uint32_t* draw_tend, uint32_t ntris, const uint32_t* indices, const float* clip,
                         const float* wn, setup_rec* recs, uint32_t rec_cap, counters* cnt);
+// The G-buffer's setup: the doubled index list, thread t = submission index t of 2 ntris: triangle
+// t >> 1, its second and third index swapped when t is odd. fp.samples must be 1.
+hipError_t launch_setup_guide(hipStream_t s, const frame_params& fp, const draw_rec* draws, uint32_t ndraws,
+                              const uint32_t* draw_tend, uint32_t ntris, const uint32_t* indices, const float* clip,
+                              const float* wn, setup_rec* recs, uint32_t rec_cap, counters* cnt);
 hipError_t launch_bin(hipStream_t s, const frame_params& fp, const setup_rec* recs, uint32_t nrec, unsigned key_bits,
                       unsigned long long* keys, uint32_t* vals);
 // range: two words per tile, the run [start, end) of the tile's pairs in the sorted arrays (0, 0: none)
@@ -70,5 +78,11 @@ hipError_t sort_pairs(hipStream_t s, void* temp, size_t& temp_bytes, const unsig
                       unsigned end_bit);
 hipError_t launch_tiles(hipStream_t s, const frame_params& fp, const setup_rec* recs, const uint32_t* vals,
                         const uint32_t* range, uint32_t* frame, float* depth_samples, uint32_t* prim_samples);
+// The G-buffer's tile kernel: normal_z = float4 (n, z) and id = the owning record's draw index per pixel.
+hipError_t launch_guide_tiles(hipStream_t s, const frame_params& fp, const setup_rec* recs, const uint32_t* vals,
+                              const uint32_t* range, void* normal_z, uint32_t* id);
+
+// the frame size of a rasterizer, for the library's other parts (the denoiser checks it against its own)
+void frame_size(const iqpt_raster* r, uint32_t* width, uint32_t* height);
 
 }  // namespace iqr

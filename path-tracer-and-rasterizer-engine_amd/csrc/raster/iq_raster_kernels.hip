@@ -94,22 +94,28 @@ constexpr float kMaxScreen = 32768.0f;   // pixels; the guard band of an 8192-wi
 __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 
+// kGuide: the G-buffer's doubled index list: thread t is submission index t of 2 ntris, triangle
+// t >> 1 of the index list, with its second and third index swapped when t is odd, so that CULL_BACK keeps
+// whichever of the two faces the camera.
+template <bool kGuide>
 __global__ void __launch_bounds__(kBlock) iqr_setup_kernel(frame_params fp, const draw_rec* __restrict__ draws,
                                                           uint32_t ndraws, const uint32_t* __restrict__ draw_tend,
                                                           uint32_t ntris, const uint32_t* __restrict__ indices,
                                                           const float* __restrict__ clip,
                                                           const float* __restrict__ wn, setup_rec* __restrict__ recs,
                                                           uint32_t rec_cap, counters* __restrict__ cnt) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= ntris) return;
-    const draw_rec& d = draws[find_draw(draw_tend, ndraws, t)];
-    const uint32_t* idx = indices + d.ibase + 3 * (size_t)(t - d.tbase);
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;          // the submission index
+    const uint32_t tri = kGuide ? t >> 1 : t;
+    if (tri >= ntris) return;
+    const draw_rec& d = draws[find_draw(draw_tend, ndraws, tri)];
+    const uint32_t* idx = indices + d.ibase + 3 * (size_t)(tri - d.tbase);
+    const bool swap = kGuide && (t & 1u);
 
     cvert poly[kMaxClipVerts], tmp[kMaxClipVerts];
     bool need_clip = false;
     unsigned all_out = 0x3fu;       // bit p: every vertex is outside plane p
     for (int k = 0; k < 3; ++k) {
-        const uint32_t vi = d.vbase + idx[k];
+        const uint32_t vi = d.vbase + idx[swap && k ? 3 - k : k];
         const float4 c = reinterpret_cast<const float4*>(clip)[vi];
         const float4 n = reinterpret_cast<const float4*>(wn)[vi];
         poly[k].v[0] = c.x; poly[k].v[1] = c.y; poly[k].v[2] = c.z; poly[k].v[3] = c.w;
@@ -201,7 +207,8 @@ __global__ void __launch_bounds__(kBlock) iqr_setup_kernel(frame_params fp, cons
         r.tile_x0y0 = tx0 | ty0 << 16;
         r.tile_x1y1 = tx1 | ty1 << 16;
         r.pair_base = (uint32_t)pair_base;
-        r.pad[0] = r.pad[1] = r.pad[2] = r.pad[3] = 0;
+        r.pad[0] = d.item;
+        r.pad[1] = r.pad[2] = r.pad[3] = 0;
         recs[slot] = r;
     }
 }
@@ -401,6 +408,96 @@ __global__ void __launch_bounds__(64) iqr_tile_kernel(frame_params fp, const set
         for (int s = 0; s < S; ++s) prim_out[pix * S + s] = prim[s];
 }
 
+// ------------------------------------------------------------------------------------------ G-buffer tiles
+// One record against one pixel centre: coverage and depth only; the lane that passes remembers the record.
+template <typename T>
+__device__ inline void guide_record(const setup_rec& r, uint32_t slot, int tox, int toy, int pcx, int pcy, float& depth,
+                                    uint32_t& owner) {
+    const int x0 = r.x0 - tox, y0 = r.y0 - toy, x1 = r.x1 - tox, y1 = r.y1 - toy, x2 = r.x2 - tox, y2 = r.y2 - toy;
+    const int dx0 = x2 - x1, dy0 = y2 - y1, dx1 = x0 - x2, dy1 = y0 - y2, dx2 = x1 - x0, dy2 = y1 - y0;
+    const T bias0 = (dy0 < 0 || (dy0 == 0 && dx0 > 0)) ? 0 : 1;
+    const T bias1 = (dy1 < 0 || (dy1 == 0 && dx1 > 0)) ? 0 : 1;
+    const T bias2 = (dy2 < 0 || (dy2 == 0 && dx2 > 0)) ? 0 : 1;
+    const T e0 = (T)dx0 * (T)(pcy - y1) - (T)dy0 * (T)(pcx - x1);
+    const T e1 = (T)dx1 * (T)(pcy - y2) - (T)dy1 * (T)(pcx - x2);
+    const T e2 = (T)dx2 * (T)(pcy - y0) - (T)dy2 * (T)(pcx - x0);
+    if (!(e0 >= bias0 && e1 >= bias1 && e2 >= bias2)) return;
+    const long long area = (long long)dx2 * (y2 - y0) - (long long)(x2 - x0) * dy2;
+    const float farea = (float)area;
+    const float b1 = (float)e1 / farea, b2 = (float)e2 / farea;
+    float z = r.z0 + b1 * r.dz1 + b2 * r.dz2;
+    z = fminf(fmaxf(z, 0.0f), 1.0f);
+    if (z < depth) {                                // LESS; in-order walk: the earlier submission keeps ties
+        depth = z;
+        owner = slot;
+    }
+}
+
+// The tile kernel's G-buffer instantiation: the same walk with one sample at the pixel centre;
+// each lane keeps the depth and the slot of the record that owns it and evaluates that record's interpolated
+// normal once, after the walk (a per-lane load of 128 bytes instead of shading every record that passes).
+__global__ void __launch_bounds__(64) iqr_guide_tile_kernel(frame_params fp, const setup_rec* __restrict__ recs,
+                                                           const uint32_t* __restrict__ vals,
+                                                           const uint32_t* __restrict__ range,
+                                                           float4* __restrict__ normal_z, uint32_t* __restrict__ id) {
+    const uint32_t tile = blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const int tox = (int)(tile % fp.ntx) * kTile * 256, toy = (int)(tile / fp.ntx) * kTile * 256;
+    const uint32_t px = (tile % fp.ntx) * kTile + (lane & 7u);
+    const uint32_t py = (tile / fp.ntx) * kTile + (lane >> 3);
+    const int pcx = (int)(lane & 7u) * 256 + 128, pcy = (int)(lane >> 3) * 256 + 128;
+
+    float depth = 1.0f;
+    uint32_t owner = kNoPrim;
+    uint32_t lo = 0, hi = 0;
+    if (range) {
+        lo = range[2 * tile];
+        hi = range[2 * tile + 1];
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    for (uint32_t chunk = lo; chunk < hi; chunk += 64) {
+        const uint32_t cn = hi - chunk < 64u ? hi - chunk : 64u;
+        const uint32_t my = lane < cn ? vals[chunk + lane] : 0u;
+        for (uint32_t j = 0; j < cn; ++j) {
+            const uint32_t slot = __builtin_amdgcn_readlane(my, j);
+            const setup_rec& r = recs[slot];
+            const int ext = imax(imax(iabs(r.x1 - r.x0), iabs(r.x2 - r.x0)), iabs(r.x2 - r.x1)) |
+                            imax(imax(iabs(r.y1 - r.y0), iabs(r.y2 - r.y0)), iabs(r.y2 - r.y1));
+            if (ext < 16384) guide_record<int>(r, slot, tox, toy, pcx, pcy, depth, owner);
+            else guide_record<long long>(r, slot, tox, toy, pcx, pcy, depth, owner);
+        }
+    }
+
+    if (px >= fp.width || py >= fp.height) return;
+    const size_t pix = (size_t)py * fp.width + px;
+    float4 out = make_float4(0.0f, 0.0f, 0.0f, depth);
+    uint32_t draw = kNoPrim;
+    if (owner != kNoPrim) {
+        const setup_rec& r = recs[owner];
+        const int x0 = r.x0 - tox, y0 = r.y0 - toy, x1 = r.x1 - tox, y1 = r.y1 - toy, x2 = r.x2 - tox, y2 = r.y2 - toy;
+        const long long e0c = (long long)(x2 - x1) * (pcy - y1) - (long long)(y2 - y1) * (pcx - x1);
+        const long long e1c = (long long)(x0 - x2) * (pcy - y2) - (long long)(y0 - y2) * (pcx - x2);
+        const long long e2c = (long long)(x1 - x0) * (pcy - y0) - (long long)(y1 - y0) * (pcx - x0);
+        const long long area = (long long)(x1 - x0) * (y2 - y0) - (long long)(x2 - x0) * (y1 - y0);
+        const float farea = (float)area;
+        // step 8's normal at the pixel centre, then iq::normalized3
+        const float p0 = (float)e0c / farea * r.rw0, p1 = (float)e1c / farea * r.rw1, p2 = (float)e2c / farea * r.rw2;
+        const float sum = p0 + p1 + p2;
+        const float nx = (p0 * r.n0[0] + p1 * r.n1[0] + p2 * r.n2[0]) / sum;
+        const float ny = (p0 * r.n0[1] + p1 * r.n1[1] + p2 * r.n2[1]) / sum;
+        const float nz = (p0 * r.n0[2] + p1 * r.n1[2] + p2 * r.n2[2]) / sum;
+        const float eps = 0.00001f;
+        if (!(fabsf(nx) < eps && fabsf(ny) < eps && fabsf(nz) < eps)) {
+            const float inv = 1.0f / sqrtf(nx * nx + ny * ny + nz * nz);
+            out.x = nx * inv; out.y = ny * inv; out.z = nz * inv;
+        }
+        draw = r.pad[0];
+    }
+    normal_z[pix] = out;
+    id[pix] = draw;
+}
+
 inline uint32_t blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 }  // namespace
@@ -417,8 +514,23 @@ hipError_t launch_setup(hipStream_t s, const frame_params& fp, const draw_rec* d
                         const uint32_t* draw_tend, uint32_t ntris, const uint32_t* indices, const float* clip,
                         const float* wn, setup_rec* recs, uint32_t rec_cap, counters* cnt) {
     if (!ntris) return hipSuccess;
-    iqr_setup_kernel<<<blocks(ntris), kBlock, 0, s>>>(fp, draws, ndraws, draw_tend, ntris, indices, clip, wn, recs,
-                                                      rec_cap, cnt);
+    iqr_setup_kernel<false><<<blocks(ntris), kBlock, 0, s>>>(fp, draws, ndraws, draw_tend, ntris, indices, clip, wn, recs,
+                                                             rec_cap, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_setup_guide(hipStream_t s, const frame_params& fp, const draw_rec* draws, uint32_t ndraws,
+                              const uint32_t* draw_tend, uint32_t ntris, const uint32_t* indices, const float* clip,
+                              const float* wn, setup_rec* recs, uint32_t rec_cap, counters* cnt) {
+    if (!ntris) return hipSuccess;
+    iqr_setup_kernel<true><<<blocks(2 * ntris), kBlock, 0, s>>>(fp, draws, ndraws, draw_tend, ntris, indices, clip, wn,
+                                                                recs, rec_cap, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_guide_tiles(hipStream_t s, const frame_params& fp, const setup_rec* recs, const uint32_t* vals,
+                              const uint32_t* range, void* normal_z, uint32_t* id) {
+    iqr_guide_tile_kernel<<<fp.ntx * fp.nty, 64, 0, s>>>(fp, recs, vals, range, static_cast<float4*>(normal_z), id);
     return hipGetLastError();
 }
 

@@ -54,14 +54,19 @@ void rasterizer::end_frame() {
     m_drawn = false;
 }
 
-void rasterizer::draw_scene(const scene& scn, std::vector<shader>& shaders, float /*dt*/) {   // rasterizer.cu:160-175
+void rasterizer::prepare(const scene& scn, std::vector<shader>& shaders) {
     // the view and projection are the shader's once the application set them (shader.cu:55-60), else the camera's
     iqpt_camera cam = m_camera->raw();
     if (!shaders.empty() && shaders[0].has_view_proj()) {
         std::memcpy(cam.view, shaders[0].view(), sizeof cam.view);
         std::memcpy(cam.projection, shaders[0].projection(), sizeof cam.projection);
     }
-    IQPT_THROW_FAILED(iqpt_raster_set_camera(m_r, &cam));
+    if (!m_have_camera || std::memcmp(cam.view, m_set_camera.view, sizeof cam.view) != 0 ||
+        std::memcmp(cam.projection, m_set_camera.projection, sizeof cam.projection) != 0) {
+        IQPT_THROW_FAILED(iqpt_raster_set_camera(m_r, &cam));
+        m_set_camera = cam;
+        m_have_camera = true;
+    }
     if (!m_have_scene || scn.revision() != m_scene_revision) {
         // mesh::setup_mesh's buffers and every model's transform, once per scene change; scene::modified() is
         // left for the path tracer, whose own packet is built from it when that engine draws next
@@ -69,6 +74,10 @@ void rasterizer::draw_scene(const scene& scn, std::vector<shader>& shaders, floa
         m_have_scene = true;
         m_scene_revision = scn.revision();
     }
+}
+
+void rasterizer::draw_scene(const scene& scn, std::vector<shader>& shaders, float /*dt*/) {   // rasterizer.cu:160-175
+    prepare(scn, shaders);
     IQPT_THROW_FAILED(iqpt_raster_draw(m_r));
     m_drawn = true;
     m_frames += 1;
@@ -78,7 +87,7 @@ void renderer::init(camera* cam, const renderer_options& opt) {                 
     if (!g_renderer) {
         rasterizer::init(cam, opt.rasterizer);
         path_tracer::init(cam, opt.path_tracer);
-        g_renderer = new renderer();
+        g_renderer = new renderer(cam, opt);
     }
 }
 
@@ -93,21 +102,44 @@ void renderer::shutdown() {                                                     
 
 renderer* renderer::get() { return g_renderer; }
 
-renderer::renderer() : m_engine_idx(engine::PATHTRACER) {                        // renderer.cu:70-78
+renderer::renderer(camera* cam, const renderer_options& opt)                     // renderer.cu:70-78
+    : m_engine_idx(engine::PATHTRACER), m_denoise(opt.denoise) {
     m_new_engine = m_engine_idx;
     m_engines[0] = rasterizer::get();
     m_engines[1] = path_tracer::get();
+    if (m_denoise.enabled) {
+        if (opt.path_tracer.world != 1)
+            throw iqpt_exception(__LINE__, __FILE__, IQPT_ERR_UNSUPPORTED, "the denoise block needs a single-GPU path tracer");
+        m_denoiser = new denoiser(cam->get_width(), cam->get_height(), opt.path_tracer.device);
+        m_denoiser->set_params(m_denoise.params);
+    }
 }
+
+renderer::~renderer() { delete m_denoiser; }
 
 void renderer::begin_frame() {                                                   // renderer.cu:45-53
     if (m_new_engine != m_engine_idx) m_engine_idx = m_new_engine;
     m_engines[(size_t)m_engine_idx]->begin_frame();
 }
 
-void renderer::end_frame() { m_engines[(size_t)m_engine_idx]->end_frame(); }
+void renderer::end_frame() {
+    m_engines[(size_t)m_engine_idx]->end_frame();
+    // the denoised frame next to the path tracer's own: the accumulator as it stands after every launch issued
+    // so far (the path tracer presents the frame before its last launch, path_tracer.cu:382-386), copied out of
+    // the context, never written
+    if (m_denoiser && m_denoise_due && m_engine_idx == engine::PATHTRACER && path_tracer::get()->frames() > 0) {
+        m_denoiser->frame(path_tracer::get()->context(), rasterizer::get()->context());
+        if (!m_denoise.ppm_path.empty()) m_denoiser->write_ppm(m_denoise.ppm_path);
+    }
+    m_denoise_due = false;
+}
 
 void renderer::draw_scene(const scene& scn, std::vector<shader>& shaders, float dt) {
     m_engines[(size_t)m_engine_idx]->draw_scene(scn, shaders, dt);
+    if (m_denoiser && m_engine_idx == engine::PATHTRACER) {
+        rasterizer::get()->prepare(scn, shaders);
+        m_denoise_due = true;
+    }
 }
 
 void renderer::reset() { static_cast<path_tracer*>(m_engines[1])->reset(); }    // renderer.cu:65-68

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "denoise/denoiser.hpp"
 #include "path_tracer.hpp"
 #include "raster/iqpt_raster.h"
 
@@ -26,6 +27,10 @@ public:
     void begin_frame() override;                 // the clear is part of the draw (rasterizer.cu:128-135)
     void end_frame() override;                   // resolve happened in the draw; reads back, writes the PPM
     void draw_scene(const scene& scene, std::vector<shader>& shaders, float dt) override;
+    // the camera and the scene of draw_scene without the draw: what a G-buffer pass (iqpt_raster_gbuffer) needs
+    // while the path tracer is the engine. A camera equal to the one already set is not set again, so the
+    // G-buffer of an unchanged view is kept.
+    void prepare(const scene& scene, std::vector<shader>& shaders);
 
     const std::vector<path_tracer::pixel>& host_pixels() const { return m_host_pixels; }
     uint64_t frames_drawn() const { return m_frames; }
@@ -39,13 +44,18 @@ private:
     camera* m_camera;
     rasterizer_options m_opt;
     std::vector<path_tracer::pixel> m_host_pixels;
-    bool m_have_scene = false, m_drawn = false;
+    bool m_have_scene = false, m_drawn = false, m_have_camera = false;
     uint64_t m_frames = 0, m_scene_revision = 0;
+    iqpt_camera m_set_camera{};                  // the camera the context has
 };
 
 struct renderer_options {
     path_tracer_options path_tracer;
     rasterizer_options rasterizer;
+    // enabled: end_frame under the path-tracing engine also filters the accumulator under the rasterizer's
+    // G-buffer and writes the result to denoise.ppm_path. The path tracer's own frame, PPM and
+    // accumulation are untouched. Single-GPU path tracer only (path_tracer.world == 1).
+    denoise_options denoise;
 };
 
 class renderer : public renderer_template {
@@ -62,13 +72,17 @@ public:
     void toggle_engine() { m_new_engine = (engine)(((int)m_new_engine + 1) % 2); }   // renderer.h:36
     void reset();                                // the path tracer's deferred reset (renderer.cu:65-68)
     engine current_engine() const { return m_engine_idx; }
+    denoiser* get_denoiser() const { return m_denoiser; }                      // NULL unless the denoise block is on
 
 private:
-    renderer();
-    ~renderer() override = default;
+    renderer(camera* cam, const renderer_options& opt);
+    ~renderer() override;
 
     engine m_new_engine, m_engine_idx;
     renderer_template* m_engines[2];
+    denoise_options m_denoise;
+    denoiser* m_denoiser = nullptr;
+    bool m_denoise_due = false;                  // the path tracer drew this frame
 };
 
 }  // namespace iqpt

@@ -166,6 +166,35 @@ RASTER_SIGNATURES = [
     ("iqpt_raster_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("iqpt_raster_stage_time", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("iqpt_raster_stats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("iqpt_raster_gbuffer", C.c_int, [_P]),
+    ("iqpt_raster_read_gbuffer", C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
+    ("iqpt_raster_gbuffer_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("iqpt_raster_gbuffer_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+]
+
+
+class DenoiseParams(C.Structure):
+    """iqpt_denoise_params (include/denoise/iqpt_denoise.h)."""
+    _fields_ = [("levels", C.c_uint32), ("normal_squarings", C.c_uint32), ("depth_sharpness", C.c_float),
+                ("colour_sharpness", C.c_float)]
+
+
+DENOISE_MAX_LEVELS = 8                         # IQPT_DENOISE_MAX_LEVELS
+# the same for include/denoise/iqpt_denoise.h (the denoiser's additions)
+DENOISE_SIGNATURES = [
+    ("iqpt_denoise_default_params", C.c_int, [C.POINTER(DenoiseParams)]),
+    ("iqpt_denoise_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_denoise_destroy", C.c_int, [_P]),
+    ("iqpt_denoise_set_params", C.c_int, [_P, C.POINTER(DenoiseParams)]),
+    ("iqpt_denoise_set_guides", C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
+    ("iqpt_denoise_set_guides_device", C.c_int, [_P, _P, _P]),
+    ("iqpt_denoise_run", C.c_int, [_P, _FP]),
+    ("iqpt_denoise_run_device", C.c_int, [_P, _P]),
+    ("iqpt_denoise_frame", C.c_int, [_P, _P, _P]),
+    ("iqpt_denoise_read", C.c_int, [_P, _FP, C.POINTER(C.c_uint8)]),
+    ("iqpt_denoise_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_denoise_sync", C.c_int, [_P]),
+    ("iqpt_denoise_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
 ]
 
 _lib = None
@@ -192,7 +221,7 @@ def load() -> C.CDLL:
     abi = lib.iqpt_abi_version() if getattr(lib, "iqpt_abi_version", None) is not None else None
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
-    for name, res, args in SIGNATURES + RASTER_SIGNATURES:
+    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:

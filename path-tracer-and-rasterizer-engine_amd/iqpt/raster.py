@@ -76,6 +76,30 @@ class Rasterizer:
                                          prim.ctypes.data_as(C.POINTER(C.c_uint32))), "iqpt_raster_read")
         return bgra, depth, prim
 
+    def gbuffer(self):
+        """The G-buffer of the uploaded scene through the current camera: normal_z [H,W,4] float32
+        (the normalised interpolated normal and the D32 depth) and id [H,W] uint32 (the draw index, RASTER_NO_PRIM
+        where nothing was drawn). One sample per pixel and two-sided, whatever `samples` is."""
+        check(self._lib.iqpt_raster_gbuffer(self._h), "iqpt_raster_gbuffer")
+        nz = np.empty((self.height, self.width, 4), dtype=np.float32)
+        ids = np.empty((self.height, self.width), dtype=np.uint32)
+        check(self._lib.iqpt_raster_read_gbuffer(self._h, nz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 ids.ctypes.data_as(C.POINTER(C.c_uint32))), "iqpt_raster_read_gbuffer")
+        return nz, ids
+
+    def gbuffer_device(self) -> tuple[int, int]:
+        """Device pointers (normal_z, id) of the G-buffer, computed if need be (iqpt_raster_gbuffer_device)."""
+        check(self._lib.iqpt_raster_gbuffer(self._h), "iqpt_raster_gbuffer")
+        a, b = C.c_void_p(), C.c_void_p()
+        check(self._lib.iqpt_raster_gbuffer_device(self._h, C.byref(a), C.byref(b)), "iqpt_raster_gbuffer_device")
+        return a.value, b.value
+
+    def gbuffer_time(self) -> tuple[float, int]:
+        """(total ms, passes) of the G-buffer passes since the last call (iqpt_raster_gbuffer_time)."""
+        ms, n = C.c_double(), C.c_uint64()
+        check(self._lib.iqpt_raster_gbuffer_time(self._h, C.byref(ms), C.byref(n)), "iqpt_raster_gbuffer_time")
+        return ms.value, n.value
+
     def copy_frame_device(self, dst_ptr: int, nbytes: int):
         check(self._lib.iqpt_raster_copy_frame_device(self._h, C.c_void_p(dst_ptr), nbytes),
               "iqpt_raster_copy_frame_device")

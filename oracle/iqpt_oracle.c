@@ -24,12 +24,13 @@
  * (BASELINE.md §3). OpenMP over 16x16 pixel tiles, dynamic schedule; per-pixel results do not
  * depend on the thread count.
  *
- * Parity status: the reference cannot be compiled in this environment (its sources include
- * <cuda.h>/<cuda_runtime.h>/<curand_kernel.h>/<d3d11.h>, which the image lacks, and stand-in
- * headers are not allowed), and it ships no tests or golden outputs (IoniqRE/image.ppm is 0
- * bytes). PARITY UNPINNED against the reference binary: this file is pinned only by
- * known-answer tests of its parts (tests/test_oracle_units.py, tests/test_xorwow.py) and by the
- * golden fixtures it generated (tests/golden/), which guard it against regressions.
+ * Parity status: the reference ships no tests or golden outputs (IoniqRE/image.ppm is 0 bytes), but its
+ * hot-path sources compile verbatim as host C++ behind stand-in headers (oracle/ref/build_ref.py). Every
+ * routine restated here is compared with the reference's own, and whole frames with its render_kernel run
+ * as a host loop, bit for bit (tests/test_ref_units.py, tests/test_ref_frames.py; recorded as
+ * tests/golden/ref_*.npz for machines without the reference). NOT pinned: cuRAND's constants (the
+ * generator is csrc/iq_xorwow.h on both sides, pinned by tests/test_xorwow.py only) and nvcc's own
+ * output (FMA contraction, libdevice).
  *
  * Floating point: compiled with -ffp-contract=off (no FMA contraction), IEEE division/sqrt, and
  * the shared transcendentals of csrc/iq_fp.h (flavour B of SURVEY.md §8c). Building with
@@ -600,9 +601,34 @@ void iqo_cosine_weighted(uint32_t* state6, float* out4) {
     for (int q = 0; q < 5; ++q) state6[q] = s.v[q];
     state6[5] = s.d;
 }
-/* One Oren-Nayar scatter; returns pdf, cos weight and attenuation.x and the outgoing ray. */
-void iqo_oren_nayar(const float* p4, const float* n4, const float* din4, uint32_t* state6,
-                    float* att4, float* pdf, float* cosw, float* ro4, float* rd4) {
+/* random::real(state, lo, hi) */
+float iqo_real(uint32_t* state6, float lo, float hi) {
+    iq_xorwow_state s;
+    for (int q = 0; q < 5; ++q) s.v[q] = state6[q];
+    s.d = state6[5];
+    const float r = rand_real(&s, lo, hi);
+    for (int q = 0; q < 5; ++q) state6[q] = s.v[q];
+    state6[5] = s.d;
+    return r;
+}
+/* One emissive scatter with the reference's light (white, strength 10); returns scatter's return value. */
+int iqo_emissive(float* att4, float* pdf, float* cosw) {
+    hit_record hr;
+    memset(&hr, 0, sizeof hr);
+    hr.mat = MAT_EMISSIVE;
+    hr.albedo = EM_ALBEDO;
+    hr.param = EM_STRENGTH;
+    scatter_record sr;
+    const int ret = emissive_scatter(&hr, &sr);
+    memcpy(att4, &sr.attenuation, 16);
+    *pdf = sr.pdf_val;
+    *cosw = sr.cos_law_weight;
+    return ret;
+}
+/* One Oren-Nayar scatter; gives pdf, cos weight, the attenuation and the outgoing ray; returns scatter's return
+ * value. */
+int iqo_oren_nayar(const float* p4, const float* n4, const float* din4, uint32_t* state6,
+                   float* att4, float* pdf, float* cosw, float* ro4, float* rd4) {
     ray_t rin, rout;
     memset(&rin, 0, sizeof rin);
     memcpy(&rin.d, din4, 16);
@@ -617,7 +643,7 @@ void iqo_oren_nayar(const float* p4, const float* n4, const float* din4, uint32_
     for (int q = 0; q < 5; ++q) s.v[q] = state6[q];
     s.d = state6[5];
     scatter_record sr;
-    oren_nayar_scatter(&rin, &hr, &sr, &rout, &s);
+    const int ret = oren_nayar_scatter(&rin, &hr, &sr, &rout, &s);
     memcpy(att4, &sr.attenuation, 16);
     *pdf = sr.pdf_val;
     *cosw = sr.cos_law_weight;
@@ -625,6 +651,7 @@ void iqo_oren_nayar(const float* p4, const float* n4, const float* din4, uint32_
     memcpy(rd4, &rout.d, 16);
     for (int q = 0; q < 5; ++q) state6[q] = s.v[q];
     state6[5] = s.d;
+    return ret;
 }
 void iqo_normal_matrix(const float* transform16, float* out16) {
     mat3 s = store3x3((const mat4*)transform16);

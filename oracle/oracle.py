@@ -1,8 +1,15 @@
 """TEST INFRASTRUCTURE ONLY — ctypes wrapper of the CPU oracle (oracle/liboracle.so).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
-The oracle restates the reference hot path on the CPU (oracle/iqpt_oracle.c); parity against the
-reference binary itself is UNPINNED (the reference cannot be built here and ships no golden data).
+The oracle restates the reference hot path on the CPU (oracle/iqpt_oracle.c).
+
+What pins it: the reference's own source, compiled verbatim as a host library by oracle/ref/build_ref.py
+(oracle/ref_oracle.py wraps it). tests/test_ref_units.py compares every routine restated here with the
+reference's, and tests/test_ref_frames.py whole frames of render_kernel, bit for bit, under the stated policy
+(contraction off, IEEE division and square root). Where the reference directory is absent the
+same comparisons run against its recorded flavour-B outputs (tests/golden/ref_*.npz).
+What stays unpinned: cuRAND's constants (the generator is csrc/iq_xorwow.h on both sides), and what nvcc makes
+of the source (FMA contraction, libdevice): no CUDA toolchain or reference binary exists here.
 """
 from __future__ import annotations
 
@@ -53,6 +60,9 @@ def load(glibc: bool = False, flavour: str | None = None) -> C.CDLL:
     lib.iqo_onb.argtypes = [_FP, _FP, _FP, _FP]
     lib.iqo_cosine_weighted.argtypes = [_UP, _FP]
     lib.iqo_oren_nayar.argtypes = [_FP, _FP, _FP, _UP, _FP, _FP, _FP, _FP, _FP]
+    lib.iqo_real.argtypes = [_UP, C.c_float, C.c_float]
+    lib.iqo_real.restype = C.c_float
+    lib.iqo_emissive.argtypes = [_FP, _FP, _FP]
     lib.iqo_normal_matrix.argtypes = [_FP, _FP]
     lib.iqo_transform_point.argtypes = [_FP, _FP, _FP]
     for fn in ("iqo_sinf", "iqo_cosf", "iqo_tanf", "iqo_acosf", "iqo_asinf"):

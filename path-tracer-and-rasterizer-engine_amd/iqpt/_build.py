@@ -198,10 +198,26 @@ def build_pair_body_libs(force: bool = False) -> list[Path]:
         return list(ex.map(lambda kw: build_lib(force, **kw), jobs))
 
 
+def build_ref(force: bool = False) -> Path | None:
+    """TEST INFRASTRUCTURE: the reference's own source as a host library (oracle/ref/build_ref.py), into the
+    git-ignored oracle/_ref/. None, quietly, where the reference directory or a compiler is absent: the build is
+    then what it is without it, and the live comparisons of tests/test_ref_*.py skip. The same where the recipe
+    itself is not in the tree (the package used with an oracle/ directory that has no ref/)."""
+    import importlib.util
+    recipe = ORACLE_DIR / "ref" / "build_ref.py"
+    if not recipe.is_file():
+        return None
+    spec = importlib.util.spec_from_file_location("iqpt_build_ref", recipe)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.build_ref(force)
+
+
 def build_all(force: bool = False) -> None:
     build_lib(force)
     build_tools(force)
     build_oracle(force)
+    build_ref(force)
     build_pair_body_libs(force)
 
 

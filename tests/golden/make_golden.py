@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Generates the golden fixtures of tests/golden/ from the CPU oracle (oracle/iqpt_oracle.c).
 
-The reference ships no golden data (IoniqRE/image.ppm is 0 bytes) and cannot be built here, so the
-fixtures pin the oracle's own output: they guard the restatement against regressions and give the
-GPU tests a CPU-free comparison. Run from the repo root:  python tests/golden/make_golden.py
+The reference ships no golden data (IoniqRE/image.ppm is 0 bytes). These fixtures pin the oracle's own
+output: they guard the restatement against regressions and give the GPU tests a CPU-free comparison at the
+benchmark's scenes and crops. What pins the oracle itself is the reference's own source built as a host
+library (oracle/ref/build_ref.py): tests/golden/make_ref_golden.py records its outputs as ref_*.npz, and
+tests/test_ref_units.py / tests/test_ref_frames.py compare the oracle with them and, where the reference
+directory exists, with the live library. Not pinned by either: cuRAND's constants (csrc/iq_xorwow.h restates
+them) and what nvcc makes of the source (contraction, libdevice).
+Run from the repo root:  python tests/golden/make_golden.py
 """
 import hashlib
 import sys

@@ -2,6 +2,11 @@
 
 CPU: the oracle reproduces them bit for bit (regression pin of the restatement).
 GPU: the HIP kernel reproduces them bit for bit without running the oracle.
+
+These fixtures are the oracle's own output. The oracle is pinned to the reference's source by
+tests/test_ref_units.py and tests/test_ref_frames.py (fixtures ref_*.npz, recorded from the reference built as
+a host library), and the kernel to the same recordings by tests/test_gpu_ref_golden.py. Not pinned anywhere:
+cuRAND's constants and nvcc's contraction and libdevice.
 """
 import ctypes as C
 import hashlib

@@ -69,7 +69,8 @@ def test_emissive_only_scene_traces_one_ray_per_path():
 
 def test_rays_per_path_of_the_app_scene_matches_the_survey_probe():
     """the reference's own source, compiled verbatim as a host loop, traced 1.61
-    rays per path on the application's default scene (max_depth 5)."""
+    rays per path on the application's default scene (max_depth 5). oracle/ref/build_ref.py now
+    reproduces that probe's build; tests/test_ref_frames.py compares its frames with the oracle's."""
     fr = oracle_render("app_default", 320, 180, 4, 5)
     assert abs(fr.rays.sum() / (320 * 180 * 4) - 1.61) < 0.02
 

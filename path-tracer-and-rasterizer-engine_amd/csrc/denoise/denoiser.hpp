@@ -40,6 +40,16 @@ public:
         IQPT_THROW_FAILED(iqpt_denoise_read(m_d, nullptr, reinterpret_cast<uint8_t*>(m_host_pixels.data())));
         m_frames += 1;
     }
+    // the same for a float4 frame already on the device and complete (the temporal result)
+    void frame_device(const void* colour_device, iqpt_raster* raster) {
+        IQPT_THROW_FAILED(iqpt_raster_gbuffer(raster));
+        const void *nz = nullptr, *id = nullptr;
+        IQPT_THROW_FAILED(iqpt_raster_gbuffer_device(raster, &nz, &id));
+        IQPT_THROW_FAILED(iqpt_denoise_set_guides_device(m_d, nz, id));
+        IQPT_THROW_FAILED(iqpt_denoise_run_device(m_d, colour_device));
+        IQPT_THROW_FAILED(iqpt_denoise_read(m_d, nullptr, reinterpret_cast<uint8_t*>(m_host_pixels.data())));
+        m_frames += 1;
+    }
     void read_linear(std::vector<float>& rgba) const {
         rgba.resize((size_t)m_width * m_height * 4);
         IQPT_THROW_FAILED(iqpt_denoise_read(m_d, rgba.data(), nullptr));

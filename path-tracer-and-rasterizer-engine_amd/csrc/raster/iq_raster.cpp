@@ -75,6 +75,7 @@ struct iqpt_raster {
     iqr::frame_params fp{};
     bool have_camera = false, have_scene = false, have_frame = false;
     dbuf camera;                  // view[16], projection[16]
+    iqpt_camera host_camera{};    // the camera as it was given (iqr::current_camera)
     geometry scene, direct;       // the uploaded scene; the vertices of the last draw_clip
     dbuf cnt, frame, depth_samples, prim_samples, sort_temp;
     lists draw_lists;             // of the last draw (iqpt_raster_read re-runs its tile kernel over them)
@@ -301,6 +302,7 @@ int iqpt_raster_set_camera(iqpt_raster* r, const iqpt_camera* cam) {
     // ordered behind the draws in flight; m is on the stack, so the copy is finished before returning
     IQR_HIP(hipMemcpyAsync(r->camera.p, m, sizeof m, hipMemcpyHostToDevice, r->stream));
     IQR_HIP(hipStreamSynchronize(r->stream));
+    r->host_camera = *cam;
     r->have_camera = true;
     r->scene.transformed = false;
     r->have_gbuffer = false;
@@ -559,3 +561,5 @@ void iqr::frame_size(const iqpt_raster* r, uint32_t* width, uint32_t* height) {
     *width = r->fp.width;
     *height = r->fp.height;
 }
+
+const iqpt_camera* iqr::current_camera(const iqpt_raster* r) { return r->have_camera ? &r->host_camera : nullptr; }

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 struct iqpt_raster;
+struct iqpt_camera;
 
 namespace iqr {
 
@@ -84,5 +85,8 @@ hipError_t launch_guide_tiles(hipStream_t s, const frame_params& fp, const setup
 
 // the frame size of a rasterizer, for the library's other parts (the denoiser checks it against its own)
 void frame_size(const iqpt_raster* r, uint32_t* width, uint32_t* height);
+// the camera of the last iqpt_raster_set_camera, whole (the temporal history needs its inverse matrices too);
+// NULL before the first one
+const iqpt_camera* current_camera(const iqpt_raster* r);
 
 }  // namespace iqr

@@ -103,7 +103,7 @@ void renderer::shutdown() {                                                     
 renderer* renderer::get() { return g_renderer; }
 
 renderer::renderer(camera* cam, const renderer_options& opt)                     // renderer.cu:70-78
-    : m_engine_idx(engine::PATHTRACER), m_denoise(opt.denoise) {
+    : m_engine_idx(engine::PATHTRACER), m_denoise(opt.denoise), m_temporal_opt(opt.temporal) {
     m_new_engine = m_engine_idx;
     m_engines[0] = rasterizer::get();
     m_engines[1] = path_tracer::get();
@@ -113,9 +113,18 @@ renderer::renderer(camera* cam, const renderer_options& opt)                    
         m_denoiser = new denoiser(cam->get_width(), cam->get_height(), opt.path_tracer.device);
         m_denoiser->set_params(m_denoise.params);
     }
+    if (m_temporal_opt.enabled) {
+        if (opt.path_tracer.world != 1)
+            throw iqpt_exception(__LINE__, __FILE__, IQPT_ERR_UNSUPPORTED, "the temporal block needs a single-GPU path tracer");
+        m_temporal = new temporal(cam->get_width(), cam->get_height(), opt.path_tracer.device);
+        m_temporal->set_params(m_temporal_opt.params);
+    }
 }
 
-renderer::~renderer() { delete m_denoiser; }
+renderer::~renderer() {
+    delete m_temporal;
+    delete m_denoiser;
+}
 
 void renderer::begin_frame() {                                                   // renderer.cu:45-53
     if (m_new_engine != m_engine_idx) m_engine_idx = m_new_engine;
@@ -127,8 +136,22 @@ void renderer::end_frame() {
     // the denoised frame next to the path tracer's own: the accumulator as it stands after every launch issued
     // so far (the path tracer presents the frame before its last launch, path_tracer.cu:382-386), copied out of
     // the context, never written
-    if (m_denoiser && m_denoise_due && m_engine_idx == engine::PATHTRACER && path_tracer::get()->frames() > 0) {
-        m_denoiser->frame(path_tracer::get()->context(), rasterizer::get()->context());
+    const bool due = m_denoise_due && m_engine_idx == engine::PATHTRACER;
+    // the temporal frame first: a view of the rasterizer's camera when it moved, then the accumulator (of
+    // frames() samples; none right after a reset: the reprojected history alone) blended with that view's history
+    if (m_temporal && due) {
+        rasterizer* rs = rasterizer::get();
+        if (m_temporal->have_view() && m_scene_revision != m_temporal_revision) m_temporal->clear();
+        if (!m_temporal->same_view(*rs->current_camera())) {
+            m_temporal->begin_view(rs->context(), *rs->current_camera());
+            m_temporal_revision = m_scene_revision;
+        }
+        m_temporal->resolve(path_tracer::get()->context());
+        if (!m_temporal_opt.ppm_path.empty()) m_temporal->write_ppm(m_temporal_opt.ppm_path);
+    }
+    if (m_denoiser && due && (m_temporal || path_tracer::get()->frames() > 0)) {
+        if (m_temporal) m_denoiser->frame_device(m_temporal->output_device(), rasterizer::get()->context());
+        else m_denoiser->frame(path_tracer::get()->context(), rasterizer::get()->context());
         if (!m_denoise.ppm_path.empty()) m_denoiser->write_ppm(m_denoise.ppm_path);
     }
     m_denoise_due = false;
@@ -136,8 +159,9 @@ void renderer::end_frame() {
 
 void renderer::draw_scene(const scene& scn, std::vector<shader>& shaders, float dt) {
     m_engines[(size_t)m_engine_idx]->draw_scene(scn, shaders, dt);
-    if (m_denoiser && m_engine_idx == engine::PATHTRACER) {
+    if ((m_denoiser || m_temporal) && m_engine_idx == engine::PATHTRACER) {
         rasterizer::get()->prepare(scn, shaders);
+        m_scene_revision = scn.revision();
         m_denoise_due = true;
     }
 }

@@ -9,6 +9,7 @@
 #include "denoise/denoiser.hpp"
 #include "path_tracer.hpp"
 #include "raster/iqpt_raster.h"
+#include "temporal/temporal.hpp"
 
 namespace iqpt {
 
@@ -35,6 +36,8 @@ public:
     const std::vector<path_tracer::pixel>& host_pixels() const { return m_host_pixels; }
     uint64_t frames_drawn() const { return m_frames; }
     iqpt_raster* context() const { return m_r; }
+    // the camera the context has (what prepare() set last); NULL before the first one
+    const iqpt_camera* current_camera() const { return m_have_camera ? &m_set_camera : nullptr; }
 
 private:
     rasterizer(camera* cam, const rasterizer_options& opt);
@@ -56,6 +59,14 @@ struct renderer_options {
     // G-buffer and writes the result to denoise.ppm_path. The path tracer's own frame, PPM and
     // accumulation are untouched. Single-GPU path tracer only (path_tracer.world == 1).
     denoise_options denoise;
+    // enabled: end_frame under the path-tracing engine also keeps a history that follows the camera (DESIGN.md
+    // §11): it begins a view when the rasterizer's camera differs from the temporal view's (or none exists),
+    // clears first when the scene's revision changed, blends the accumulator with the view's history and
+    // writes the result to temporal.ppm_path. With denoise on as well, the denoiser filters that result
+    // instead of the accumulator. The path tracer's own frame, PPM and accumulation are untouched. Single-GPU
+    // path tracer only. World positions come from the camera's inverse matrices, so a view and projection set
+    // through shader::update_view_proj must be the camera's own.
+    temporal_options temporal;
 };
 
 class renderer : public renderer_template {
@@ -73,6 +84,7 @@ public:
     void reset();                                // the path tracer's deferred reset (renderer.cu:65-68)
     engine current_engine() const { return m_engine_idx; }
     denoiser* get_denoiser() const { return m_denoiser; }                      // NULL unless the denoise block is on
+    temporal* get_temporal() const { return m_temporal; }                      // NULL unless the temporal block is on
 
 private:
     renderer(camera* cam, const renderer_options& opt);
@@ -83,6 +95,10 @@ private:
     denoise_options m_denoise;
     denoiser* m_denoiser = nullptr;
     bool m_denoise_due = false;                  // the path tracer drew this frame
+    temporal_options m_temporal_opt;
+    temporal* m_temporal = nullptr;
+    uint64_t m_temporal_revision = 0;            // the scene revision of the temporal view
+    uint64_t m_scene_revision = 0;               // of the scene drawn last
 };
 
 }  // namespace iqpt

@@ -6,6 +6,9 @@
 //   iqpt_cli --engine raster --preset cornell --samples 4 --out preview.ppm     (the rasterized preview)
 //   iqpt_cli --preset cornell_lit --spp 4 --denoise [--denoise-levels 3] --out noisy.ppm --out-denoised clean.ppm
 //     (the path tracer through iqpt::renderer with the denoise block on: both frames are written)
+//   iqpt_cli --preset cornell_lit --spp 1 --temporal --views 8 --step-x 0.05 --out last.ppm --out-temporal kept.ppm
+//     (K views, the camera moved by D along x per view and reset between them, --spp samples per view; the last
+//     view's own frame and its temporal frame, which keeps the earlier views' samples, are written)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,13 +19,15 @@
 #include "raster/rasterizer.hpp"
 
 int main(int argc, char** argv) {
-    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised;
+    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised, out_temporal;
     int width = 640, height = 360, spp = 16, launches = 1, max_depth = 8, device = 0, samples = 4, denoise_levels = -1;
-    bool denoise = false;
+    int views = -1;
+    float step_x = 0.0f;
+    bool denoise = false, temporal = false, have_step = false;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--denoise") {                  // the only option without a value
-            denoise = true;
+        if (k == "--denoise" || k == "--temporal") {   // the options without a value
+            (k == "--denoise" ? denoise : temporal) = true;
             i -= 1;
             continue;
         }
@@ -31,6 +36,12 @@ int main(int argc, char** argv) {
         if (k == "--preset") preset = v;
         else if (k == "--out-denoised") out_denoised = v;
         else if (k == "--denoise-levels") denoise_levels = std::atoi(v);
+        else if (k == "--out-temporal") out_temporal = v;
+        else if (k == "--views") views = std::atoi(v);
+        else if (k == "--step-x") {
+            step_x = (float)std::atof(v);
+            have_step = true;
+        }
         else if (k == "--out") out = v;
         else if (k == "--width") width = std::atoi(v);
         else if (k == "--height") height = std::atoi(v);
@@ -57,10 +68,65 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--denoise-levels and --out-denoised need --denoise\n");
         return 2;
     }
+    if (temporal && (engine != "pt" || denoise || out_temporal.empty() || views == 0 || views < -1)) {
+        std::fprintf(stderr, "--temporal goes with the path tracer alone, needs --out-temporal PATH and --views >= 1\n");
+        return 2;
+    }
+    if (!temporal && (views != -1 || have_step || !out_temporal.empty())) {
+        std::fprintf(stderr, "--views, --step-x and --out-temporal need --temporal\n");
+        return 2;
+    }
     try {
         iqpt::camera cam((uint16_t)width, (uint16_t)height);
         iqpt::scene scn;
         scn.add_preset(preset);
+        if (temporal) {
+            // the contexts themselves (the facade's camera never moves): every view sets the moved camera on the
+            // path tracer and the rasterizer, resets the accumulation, begins a temporal view from the G-buffer
+            // and resolves the view's samples into it
+            if (views < 0) views = 1;
+            iqpt_ctx* ctx = nullptr;
+            iqpt_raster* rs = nullptr;
+            IQPT_THROW_FAILED(iqpt_create(device, (uint32_t)width, (uint32_t)height, nullptr, IQPT_DEFAULT_SEED, max_depth, &ctx));
+            IQPT_THROW_FAILED(iqpt_raster_create(device, (uint32_t)width, (uint32_t)height, 1, &rs));
+            {
+                iqpt::temporal tmp((uint32_t)width, (uint32_t)height, device);
+                const iqpt_packet_desc pk = scn.build_packet();
+                IQPT_THROW_FAILED(iqpt_upload_packet(ctx, &pk));
+                IQPT_THROW_FAILED(iqpt_raster_upload_scene(rs, scn.handle()));
+                for (int k = 0; k < views; ++k) {
+                    iqpt_camera moved;
+                    float pos[4];
+                    std::memcpy(pos, cam.raw().position, sizeof pos);
+                    pos[0] = pos[0] + step_x * (float)k;
+                    IQPT_THROW_FAILED(iqpt_camera_init(&moved, (uint16_t)width, (uint16_t)height, cam.raw().fovh, 0.01f, 100.0f,
+                                                       pos, cam.raw().forward));
+                    IQPT_THROW_FAILED(iqpt_set_camera(ctx, &moved));
+                    IQPT_THROW_FAILED(iqpt_reset(ctx));
+                    IQPT_THROW_FAILED(iqpt_raster_set_camera(rs, &moved));
+                    tmp.begin_view(rs, moved);
+                    for (int l = 0; l < launches; ++l) IQPT_THROW_FAILED(iqpt_render(ctx, (uint32_t)spp));
+                    tmp.resolve(ctx);
+                }
+                std::vector<uint8_t> bgra((size_t)width * height * 4);
+                IQPT_THROW_FAILED(iqpt_read(ctx, nullptr, bgra.data()));
+                IQPT_THROW_FAILED(iqpt_write_ppm(out.c_str(), (uint32_t)width, (uint32_t)height, bgra.data()));
+                tmp.write_ppm(out_temporal);
+                uint64_t frames = 0, guided = 0, valid = 0, nviews = 0, nresolves = 0;
+                double view_ms = 0.0, resolve_ms = 0.0;
+                IQPT_THROW_FAILED(iqpt_frame_count(ctx, &frames));
+                IQPT_THROW_FAILED(iqpt_temporal_stats(tmp.context(), &guided, &valid));
+                IQPT_THROW_FAILED(iqpt_temporal_time(tmp.context(), &view_ms, &nviews, &resolve_ms, &nresolves));
+                std::printf("{\"preset\": \"%s\", \"views\": %d, \"step_x\": %g, \"frames\": %llu, \"out\": \"%s\", "
+                            "\"out_temporal\": \"%s\", \"guided\": %llu, \"valid\": %llu, \"view_ms\": %.4f, "
+                            "\"resolve_ms\": %.4f}\n",
+                            preset.c_str(), views, (double)step_x, (unsigned long long)frames, out.c_str(), out_temporal.c_str(),
+                            (unsigned long long)guided, (unsigned long long)valid, view_ms, resolve_ms);
+            }
+            iqpt_raster_destroy(rs);
+            iqpt_destroy(ctx);
+            return 0;
+        }
         if (engine == "raster") {
             // the other engine (rasterizer.cu): one rasterized frame, presented as PPM by end_frame
             iqpt::rasterizer_options ro;

@@ -197,6 +197,36 @@ DENOISE_SIGNATURES = [
     ("iqpt_denoise_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
 ]
 
+
+
+class TemporalParams(C.Structure):
+    """iqpt_temporal_params (include/temporal/iqpt_temporal.h)."""
+    _fields_ = [("normal_min", C.c_float), ("plane_tolerance", C.c_float), ("max_history", C.c_uint32)]
+
+
+TEMPORAL_MAX_HISTORY = 1 << 24                 # IQPT_TEMPORAL_MAX_HISTORY
+# the same for include/temporal/iqpt_temporal.h (temporal reprojection's additions)
+TEMPORAL_SIGNATURES = [
+    ("iqpt_temporal_default_params", C.c_int, [C.POINTER(TemporalParams)]),
+    ("iqpt_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_temporal_destroy", C.c_int, [_P]),
+    ("iqpt_temporal_set_params", C.c_int, [_P, C.POINTER(TemporalParams)]),
+    ("iqpt_temporal_begin_view", C.c_int, [_P, C.POINTER(Camera), _FP, C.POINTER(C.c_uint32)]),
+    ("iqpt_temporal_begin_view_device", C.c_int, [_P, C.POINTER(Camera), _P, _P]),
+    ("iqpt_temporal_begin_view_raster", C.c_int, [_P, _P]),
+    ("iqpt_temporal_clear", C.c_int, [_P]),
+    ("iqpt_temporal_resolve", C.c_int, [_P, _FP, C.c_uint64]),
+    ("iqpt_temporal_resolve_device", C.c_int, [_P, _P, C.c_uint64]),
+    ("iqpt_temporal_resolve_ctx", C.c_int, [_P, _P]),
+    ("iqpt_temporal_read", C.c_int, [_P, _FP, C.POINTER(C.c_uint8)]),
+    ("iqpt_temporal_output_device", C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    ("iqpt_temporal_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_temporal_sync", C.c_int, [_P]),
+    ("iqpt_temporal_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_uint64)]),
+    ("iqpt_temporal_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+]
+
 _lib = None
 
 
@@ -221,7 +251,7 @@ def load() -> C.CDLL:
     abi = lib.iqpt_abi_version() if getattr(lib, "iqpt_abi_version", None) is not None else None
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
-    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES:
+    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:

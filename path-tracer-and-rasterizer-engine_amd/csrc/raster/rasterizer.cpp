@@ -103,7 +103,7 @@ void renderer::shutdown() {                                                     
 renderer* renderer::get() { return g_renderer; }
 
 renderer::renderer(camera* cam, const renderer_options& opt)                     // renderer.cu:70-78
-    : m_engine_idx(engine::PATHTRACER), m_denoise(opt.denoise), m_temporal_opt(opt.temporal) {
+    : m_engine_idx(engine::PATHTRACER), m_denoise(opt.denoise), m_temporal_opt(opt.temporal), m_svgf_opt(opt.svgf) {
     m_new_engine = m_engine_idx;
     m_engines[0] = rasterizer::get();
     m_engines[1] = path_tracer::get();
@@ -119,9 +119,16 @@ renderer::renderer(camera* cam, const renderer_options& opt)                    
         m_temporal = new temporal(cam->get_width(), cam->get_height(), opt.path_tracer.device);
         m_temporal->set_params(m_temporal_opt.params);
     }
+    if (m_svgf_opt.enabled) {
+        if (opt.path_tracer.world != 1)
+            throw iqpt_exception(__LINE__, __FILE__, IQPT_ERR_UNSUPPORTED, "the svgf block needs a single-GPU path tracer");
+        m_svgf = new svgf(cam->get_width(), cam->get_height(), opt.path_tracer.device);
+        m_svgf->set_params(m_svgf_opt.params);
+    }
 }
 
 renderer::~renderer() {
+    delete m_svgf;
     delete m_temporal;
     delete m_denoiser;
 }
@@ -154,12 +161,23 @@ void renderer::end_frame() {
         else m_denoiser->frame(path_tracer::get()->context(), rasterizer::get()->context());
         if (!m_denoise.ppm_path.empty()) m_denoiser->write_ppm(m_denoise.ppm_path);
     }
+    // variance-guided filtering, on its own two histories: the same view logic as the temporal block
+    if (m_svgf && due) {
+        rasterizer* rs = rasterizer::get();
+        if (m_svgf->have_view() && m_scene_revision != m_svgf_revision) m_svgf->clear();
+        if (!m_svgf->same_view(*rs->current_camera())) {
+            m_svgf->begin_view(rs->context(), *rs->current_camera());
+            m_svgf_revision = m_scene_revision;
+        }
+        m_svgf->resolve(path_tracer::get()->context());
+        if (!m_svgf_opt.ppm_path.empty()) m_svgf->write_ppm(m_svgf_opt.ppm_path);
+    }
     m_denoise_due = false;
 }
 
 void renderer::draw_scene(const scene& scn, std::vector<shader>& shaders, float dt) {
     m_engines[(size_t)m_engine_idx]->draw_scene(scn, shaders, dt);
-    if ((m_denoiser || m_temporal) && m_engine_idx == engine::PATHTRACER) {
+    if ((m_denoiser || m_temporal || m_svgf) && m_engine_idx == engine::PATHTRACER) {
         rasterizer::get()->prepare(scn, shaders);
         m_scene_revision = scn.revision();
         m_denoise_due = true;

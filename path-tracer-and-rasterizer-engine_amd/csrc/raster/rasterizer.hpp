@@ -9,6 +9,7 @@
 #include "denoise/denoiser.hpp"
 #include "path_tracer.hpp"
 #include "raster/iqpt_raster.h"
+#include "svgf/svgf.hpp"
 #include "temporal/temporal.hpp"
 
 namespace iqpt {
@@ -67,6 +68,12 @@ struct renderer_options {
     // path tracer only. World positions come from the camera's inverse matrices, so a view and projection set
     // through shader::update_view_proj must be the camera's own.
     temporal_options temporal;
+    // enabled: end_frame under the path-tracing engine also runs variance-guided filtering, as the
+    // temporal block runs its history: it begins a view when the rasterizer's camera differs from the object's
+    // (or none exists), clears first when the scene's revision changed, resolves the accumulator and writes the
+    // filtered frame to svgf.ppm_path. Independent of the temporal and denoise blocks (it owns its two histories).
+    // The path tracer's own frame, PPM and accumulation are untouched. Single-GPU path tracer only.
+    svgf_options svgf;
 };
 
 class renderer : public renderer_template {
@@ -85,6 +92,7 @@ public:
     engine current_engine() const { return m_engine_idx; }
     denoiser* get_denoiser() const { return m_denoiser; }                      // NULL unless the denoise block is on
     temporal* get_temporal() const { return m_temporal; }                      // NULL unless the temporal block is on
+    svgf* get_svgf() const { return m_svgf; }                                  // NULL unless the svgf block is on
 
 private:
     renderer(camera* cam, const renderer_options& opt);
@@ -99,6 +107,9 @@ private:
     temporal* m_temporal = nullptr;
     uint64_t m_temporal_revision = 0;            // the scene revision of the temporal view
     uint64_t m_scene_revision = 0;               // of the scene drawn last
+    svgf_options m_svgf_opt;
+    svgf* m_svgf = nullptr;
+    uint64_t m_svgf_revision = 0;                // the scene revision of the svgf view
 };
 
 }  // namespace iqpt

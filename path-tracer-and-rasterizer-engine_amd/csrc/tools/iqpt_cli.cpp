@@ -9,9 +9,12 @@
 //   iqpt_cli --preset cornell_lit --spp 1 --temporal --views 8 --step-x 0.05 --out last.ppm --out-temporal kept.ppm
 //     (K views, the camera moved by D along x per view and reset between them, --spp samples per view; the last
 //     view's own frame and its temporal frame, which keeps the earlier views' samples, are written)
+//   iqpt_cli --preset cornell_lit --spp 1 --svgf --views 8 --step-x 0.05 --out last.ppm --out-svgf filtered.ppm
+//     (the same sequence through variance-guided filtering; may be combined with --temporal)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -19,15 +22,15 @@
 #include "raster/rasterizer.hpp"
 
 int main(int argc, char** argv) {
-    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised, out_temporal;
+    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised, out_temporal, out_svgf;
     int width = 640, height = 360, spp = 16, launches = 1, max_depth = 8, device = 0, samples = 4, denoise_levels = -1;
     int views = -1;
     float step_x = 0.0f;
-    bool denoise = false, temporal = false, have_step = false;
+    bool denoise = false, temporal = false, svgf = false, have_step = false;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--denoise" || k == "--temporal") {   // the options without a value
-            (k == "--denoise" ? denoise : temporal) = true;
+        if (k == "--denoise" || k == "--temporal" || k == "--svgf") {   // the options without a value
+            (k == "--denoise" ? denoise : k == "--temporal" ? temporal : svgf) = true;
             i -= 1;
             continue;
         }
@@ -37,6 +40,7 @@ int main(int argc, char** argv) {
         else if (k == "--out-denoised") out_denoised = v;
         else if (k == "--denoise-levels") denoise_levels = std::atoi(v);
         else if (k == "--out-temporal") out_temporal = v;
+        else if (k == "--out-svgf") out_svgf = v;
         else if (k == "--views") views = std::atoi(v);
         else if (k == "--step-x") {
             step_x = (float)std::atof(v);
@@ -72,25 +76,40 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--temporal goes with the path tracer alone, needs --out-temporal PATH and --views >= 1\n");
         return 2;
     }
-    if (!temporal && (views != -1 || have_step || !out_temporal.empty())) {
-        std::fprintf(stderr, "--views, --step-x and --out-temporal need --temporal\n");
+    if (svgf && (engine != "pt" || denoise || out_svgf.empty() || views == 0 || views < -1)) {
+        std::fprintf(stderr, "--svgf goes with the path tracer (and --temporal), needs --out-svgf PATH and --views >= 1\n");
+        return 2;
+    }
+    if (!temporal && !out_temporal.empty()) {
+        std::fprintf(stderr, "--out-temporal needs --temporal\n");
+        return 2;
+    }
+    if (!svgf && !out_svgf.empty()) {
+        std::fprintf(stderr, "--out-svgf needs --svgf\n");
+        return 2;
+    }
+    if (!temporal && !svgf && (views != -1 || have_step)) {
+        std::fprintf(stderr, "--views and --step-x need --temporal or --svgf\n");
         return 2;
     }
     try {
         iqpt::camera cam((uint16_t)width, (uint16_t)height);
         iqpt::scene scn;
         scn.add_preset(preset);
-        if (temporal) {
+        if (temporal || svgf) {
             // the contexts themselves (the facade's camera never moves): every view sets the moved camera on the
-            // path tracer and the rasterizer, resets the accumulation, begins a temporal view from the G-buffer
-            // and resolves the view's samples into it
+            // path tracer and the rasterizer, resets the accumulation, begins a temporal view (an svgf view, or both)
+            // from the G-buffer and resolves the view's samples into it
             if (views < 0) views = 1;
             iqpt_ctx* ctx = nullptr;
             iqpt_raster* rs = nullptr;
             IQPT_THROW_FAILED(iqpt_create(device, (uint32_t)width, (uint32_t)height, nullptr, IQPT_DEFAULT_SEED, max_depth, &ctx));
             IQPT_THROW_FAILED(iqpt_raster_create(device, (uint32_t)width, (uint32_t)height, 1, &rs));
             {
-                iqpt::temporal tmp((uint32_t)width, (uint32_t)height, device);
+                std::unique_ptr<iqpt::temporal> tmp;
+                std::unique_ptr<iqpt::svgf> vgf;
+                if (temporal) tmp.reset(new iqpt::temporal((uint32_t)width, (uint32_t)height, device));
+                if (svgf) vgf.reset(new iqpt::svgf((uint32_t)width, (uint32_t)height, device));
                 const iqpt_packet_desc pk = scn.build_packet();
                 IQPT_THROW_FAILED(iqpt_upload_packet(ctx, &pk));
                 IQPT_THROW_FAILED(iqpt_raster_upload_scene(rs, scn.handle()));
@@ -104,24 +123,42 @@ int main(int argc, char** argv) {
                     IQPT_THROW_FAILED(iqpt_set_camera(ctx, &moved));
                     IQPT_THROW_FAILED(iqpt_reset(ctx));
                     IQPT_THROW_FAILED(iqpt_raster_set_camera(rs, &moved));
-                    tmp.begin_view(rs, moved);
+                    if (tmp) tmp->begin_view(rs, moved);
+                    if (vgf) vgf->begin_view(rs, moved);
                     for (int l = 0; l < launches; ++l) IQPT_THROW_FAILED(iqpt_render(ctx, (uint32_t)spp));
-                    tmp.resolve(ctx);
+                    if (tmp) tmp->resolve(ctx);
+                    if (vgf) vgf->resolve(ctx);
                 }
                 std::vector<uint8_t> bgra((size_t)width * height * 4);
                 IQPT_THROW_FAILED(iqpt_read(ctx, nullptr, bgra.data()));
                 IQPT_THROW_FAILED(iqpt_write_ppm(out.c_str(), (uint32_t)width, (uint32_t)height, bgra.data()));
-                tmp.write_ppm(out_temporal);
                 uint64_t frames = 0, guided = 0, valid = 0, nviews = 0, nresolves = 0;
                 double view_ms = 0.0, resolve_ms = 0.0;
                 IQPT_THROW_FAILED(iqpt_frame_count(ctx, &frames));
-                IQPT_THROW_FAILED(iqpt_temporal_stats(tmp.context(), &guided, &valid));
-                IQPT_THROW_FAILED(iqpt_temporal_time(tmp.context(), &view_ms, &nviews, &resolve_ms, &nresolves));
-                std::printf("{\"preset\": \"%s\", \"views\": %d, \"step_x\": %g, \"frames\": %llu, \"out\": \"%s\", "
-                            "\"out_temporal\": \"%s\", \"guided\": %llu, \"valid\": %llu, \"view_ms\": %.4f, "
-                            "\"resolve_ms\": %.4f}\n",
-                            preset.c_str(), views, (double)step_x, (unsigned long long)frames, out.c_str(), out_temporal.c_str(),
-                            (unsigned long long)guided, (unsigned long long)valid, view_ms, resolve_ms);
+                if (vgf) {
+                    vgf->write_ppm(out_svgf);
+                    uint64_t spatial = 0;
+                    double moments_ms = 0.0, variance_ms = 0.0, level_ms[IQPT_SVGF_MAX_LEVELS] = {}, filter_ms = 0.0;
+                    IQPT_THROW_FAILED(iqpt_svgf_stats(vgf->context(), &guided, &valid, &spatial));
+                    IQPT_THROW_FAILED(iqpt_svgf_time(vgf->context(), &moments_ms, &variance_ms, level_ms, &nresolves, nullptr, nullptr));
+                    for (double ms : level_ms) filter_ms += ms;
+                    std::printf("{\"preset\": \"%s\", \"views\": %d, \"step_x\": %g, \"frames\": %llu, \"out\": \"%s\", "
+                                "\"out_svgf\": \"%s\", \"guided\": %llu, \"valid\": %llu, \"spatial\": %llu, "
+                                "\"moments_ms\": %.4f, \"variance_ms\": %.4f, \"levels_ms\": %.4f}\n",
+                                preset.c_str(), views, (double)step_x, (unsigned long long)frames, out.c_str(), out_svgf.c_str(),
+                                (unsigned long long)guided, (unsigned long long)valid, (unsigned long long)spatial, moments_ms,
+                                variance_ms, filter_ms);
+                }
+                if (tmp) {      // the last line of the output, as before
+                    tmp->write_ppm(out_temporal);
+                    IQPT_THROW_FAILED(iqpt_temporal_stats(tmp->context(), &guided, &valid));
+                    IQPT_THROW_FAILED(iqpt_temporal_time(tmp->context(), &view_ms, &nviews, &resolve_ms, &nresolves));
+                    std::printf("{\"preset\": \"%s\", \"views\": %d, \"step_x\": %g, \"frames\": %llu, \"out\": \"%s\", "
+                                "\"out_temporal\": \"%s\", \"guided\": %llu, \"valid\": %llu, \"view_ms\": %.4f, "
+                                "\"resolve_ms\": %.4f}\n",
+                                preset.c_str(), views, (double)step_x, (unsigned long long)frames, out.c_str(),
+                                out_temporal.c_str(), (unsigned long long)guided, (unsigned long long)valid, view_ms, resolve_ms);
+                }
             }
             iqpt_raster_destroy(rs);
             iqpt_destroy(ctx);

@@ -35,6 +35,7 @@ FACADE_TEST_PATH = PKG_DIR / "test_facade"
 RASTER_FACADE_TEST_PATH = PKG_DIR / "test_raster_facade"
 DENOISE_FACADE_TEST_PATH = PKG_DIR / "test_denoise_facade"
 TEMPORAL_FACADE_TEST_PATH = PKG_DIR / "test_temporal_facade"
+SVGF_FACADE_TEST_PATH = PKG_DIR / "test_svgf_facade"
 
 ARCH = os.environ.get("IQPT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
@@ -51,7 +52,9 @@ LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tra
                # the rasterizer-guided denoiser, likewise outside that identity
                "denoise/iq_denoise_kernels.hip", "denoise/iq_denoise.cpp",
                # temporal reprojection, likewise
-               "temporal/iq_temporal_kernels.hip", "temporal/iq_temporal.cpp"]
+               "temporal/iq_temporal_kernels.hip", "temporal/iq_temporal.cpp",
+               # variance-guided filtering, likewise
+               "svgf/iq_svgf_kernels.hip", "svgf/iq_svgf.cpp"]
 
 
 def _run(cmd: list[str], cwd: Path | None = None) -> None:
@@ -84,9 +87,13 @@ def _temporal_headers() -> list[Path]:
     return sorted((CSRC / "temporal").glob("*.hpp")) + sorted((INCLUDE / "temporal").glob("*.h"))
 
 
+def _svgf_headers() -> list[Path]:
+    return sorted((CSRC / "svgf").glob("*.hpp")) + sorted((INCLUDE / "svgf").glob("*.h"))
+
+
 def _deps() -> list[Path]:
     """Every header a library object or a tool may include."""
-    return _headers() + _raster_headers() + _denoise_headers() + _temporal_headers()
+    return _headers() + _raster_headers() + _denoise_headers() + _temporal_headers() + _svgf_headers()
 
 
 def kernel_source_sha16() -> str:
@@ -132,14 +139,15 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
 
 def build_tools(force: bool = False) -> list[Path]:
     """C++ programs over the facades: the headless CLI, the path_tracer facade test, the two-engine renderer test
-    and the tests of the renderer's denoise and temporal blocks."""
+    and the tests of the renderer's denoise, temporal and svgf blocks."""
     lib = build_lib(force)
     out = []
     for src, dst in ((CSRC / "tools" / "iqpt_cli.cpp", CLI_PATH),
                      (CSRC / "tools" / "test_facade.cpp", FACADE_TEST_PATH),
                      (CSRC / "tools" / "test_raster_facade.cpp", RASTER_FACADE_TEST_PATH),
                      (CSRC / "tools" / "test_denoise_facade.cpp", DENOISE_FACADE_TEST_PATH),
-                     (CSRC / "tools" / "test_temporal_facade.cpp", TEMPORAL_FACADE_TEST_PATH)):
+                     (CSRC / "tools" / "test_temporal_facade.cpp", TEMPORAL_FACADE_TEST_PATH),
+                     (CSRC / "tools" / "test_svgf_facade.cpp", SVGF_FACADE_TEST_PATH)):
         if not src.exists():
             continue
         if force or not _newer(dst, [src, lib] + _deps()):

@@ -227,6 +227,37 @@ TEMPORAL_SIGNATURES = [
     ("iqpt_temporal_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 ]
 
+
+class SvgfParams(C.Structure):
+    """iqpt_svgf_params (include/svgf/iqpt_svgf.h)."""
+    _fields_ = [("normal_min", C.c_float), ("plane_tolerance", C.c_float), ("max_history", C.c_uint32),
+                ("min_history", C.c_uint32), ("levels", C.c_uint32), ("normal_squarings", C.c_uint32),
+                ("depth_sharpness", C.c_float), ("colour_sigma", C.c_float), ("variance_floor", C.c_float)]
+
+
+SVGF_MAX_LEVELS = 8                            # IQPT_SVGF_MAX_LEVELS
+_DP = C.POINTER(C.c_double)
+# the same for include/svgf/iqpt_svgf.h (variance-guided filtering's additions)
+SVGF_SIGNATURES = [
+    ("iqpt_svgf_default_params", C.c_int, [C.POINTER(SvgfParams)]),
+    ("iqpt_svgf_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_svgf_destroy", C.c_int, [_P]),
+    ("iqpt_svgf_set_params", C.c_int, [_P, C.POINTER(SvgfParams)]),
+    ("iqpt_svgf_begin_view", C.c_int, [_P, C.POINTER(Camera), _FP, C.POINTER(C.c_uint32)]),
+    ("iqpt_svgf_begin_view_device", C.c_int, [_P, C.POINTER(Camera), _P, _P]),
+    ("iqpt_svgf_begin_view_raster", C.c_int, [_P, _P]),
+    ("iqpt_svgf_clear", C.c_int, [_P]),
+    ("iqpt_svgf_resolve", C.c_int, [_P, _FP, C.c_uint64]),
+    ("iqpt_svgf_resolve_device", C.c_int, [_P, _P, C.c_uint64]),
+    ("iqpt_svgf_resolve_ctx", C.c_int, [_P, _P]),
+    ("iqpt_svgf_read", C.c_int, [_P, _FP, C.POINTER(C.c_uint8)]),
+    ("iqpt_svgf_read_stages", C.c_int, [_P, _FP, _FP]),
+    ("iqpt_svgf_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_svgf_sync", C.c_int, [_P]),
+    ("iqpt_svgf_time", C.c_int, [_P, _DP, _DP, _DP, C.POINTER(C.c_uint64), _DP, _DP]),
+    ("iqpt_svgf_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+]
+
 _lib = None
 
 
@@ -251,7 +282,7 @@ def load() -> C.CDLL:
     abi = lib.iqpt_abi_version() if getattr(lib, "iqpt_abi_version", None) is not None else None
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
-    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES:
+    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES + SVGF_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:

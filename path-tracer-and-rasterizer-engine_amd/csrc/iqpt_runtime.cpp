@@ -3469,6 +3469,75 @@ int iqpt_debug_cull_tile(const iqpt_camera* cam, uint32_t xa, uint32_t xb, uint3
     return b.ok ? 1 : 0;
 }
 
+/* Internal (tests/test_certain.py): the host build of iq_interval.h's tri_certain for one bundle of camera rays,
+ * same conventions as iqpt_debug_cull_tile. Writes 1 per triangle that every ray of the bundle is proved to hit
+ * as a first hit; returns 0 with all flags 0 if the bundle is unbounded (nothing is certain). */
+int iqpt_debug_certain_tile(const iqpt_camera* cam, uint32_t xa, uint32_t xb, uint32_t ya, uint32_t yb,
+                            const float* tris, uint32_t ntri, uint8_t* certain_out) {
+    if (!cam || (ntri && (!tris || !certain_out))) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    iqiv::camera_in ci;
+    ci.width = cam->width;
+    ci.height = cam->height;
+    ci.rcp_width = 0.0f;
+    ci.rcp_height = 0.0f;
+    ci.inv_proj = cam->inv_proj;
+    ci.inv_view = cam->inv_view;
+    uint32_t cc = 0;
+    cam_constants(*cam, &cc, &ci.near_rw, &ci.far_rw);
+    ci.cam_const = (int)cc;
+    const iqiv::bundle b = iqiv::camera_bundle(ci, xa, xb, ya, yb);
+    for (uint32_t k = 0; k < ntri; ++k)
+        certain_out[k] = b.ok && iqiv::tri_certain(b, tris + 9 * k, tris + 9 * k + 3, tris + 9 * k + 6) ? 1 : 0;
+    return b.ok ? 1 : 0;
+}
+
+/* Internal (tests/test_gpu_proofs.py): what the proof kernels wrote and read for the current masks, as 32-bit
+ * words copied from the device after a synchronise. *n = the buffer's size in words (0 where it was not built);
+ * copied into out if out is not NULL (cap words must hold it). IQPT_ERR_NOT_READY without valid masks (before the
+ * first launch or iqpt_prepare, or after a change that invalidates them). what:
+ *   0  12 words: cull_ntx, cull_nty, cull_wt, cull_stride, ntri, nsph, certain masks built, lists built,
+ *      list entries, per-pixel masks built, per-pixel mask words, 0
+ *   1  d_cull: ntiles x stride words (iqpt_bin_kernel)
+ *   2  d_certain: 2 ntiles words of certain-hit masks, then 2 ntiles of certain-miss masks (iqpt_certain_kernel)
+ *   3  d_list: the candidate lists, then the triangle offsets (ntiles + 1) and the sphere offsets (ntiles + 1)
+ *   4  d_pmask: the per-tile word offsets (ntiles + 1), the per-pixel mask words, then iqpt_pixel_mask_kernel's
+ *      2 ntiles certain words
+ *   5  d_tris: ntri x 12 floats (v0, e1, e2 world space, three pad words)
+ *   6  d_sph: nsph x 4 floats (centre, radius) */
+int iqpt_debug_read_proofs(iqpt_ctx* c, int what, uint32_t* out, uint64_t cap, uint64_t* n) {
+    if (!c || !n) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    *n = 0;
+    if (!c->have_camera || !c->have_packet || !c->cull_valid) return iqpt::fail(IQPT_ERR_NOT_READY, "no valid masks");
+    int st = enter(c);
+    if (st) return st;
+    IQPT_HIP(hipStreamSynchronize(c->stream));
+    const uint64_t nt = (uint64_t)c->cull_ntx * c->cull_nty;
+    const bool masks = nt * c->cull_stride > 0 && c->d_cull;
+    const bool lists = masks && c->d_list;
+    const bool pm = lists && c->d_pmask;
+    const uint32_t grid[12] = {c->cull_ntx, c->cull_nty, c->cull_wt, c->cull_stride, c->ntri, c->nsph,
+                               masks && c->certain_valid && c->d_certain ? 1u : 0u, lists ? 1u : 0u,
+                               lists ? (uint32_t)c->list_total : 0u, pm ? 1u : 0u, pm ? (uint32_t)c->pmask_words : 0u, 0u};
+    const void* src = nullptr;
+    uint64_t words = 0;
+    switch (what) {
+    case 0: words = 12; break;
+    case 1: if (masks) { src = c->d_cull; words = nt * c->cull_stride; } break;
+    case 2: if (grid[6]) { src = c->d_certain; words = 4 * nt; } break;
+    case 3: if (lists) { src = c->d_list; words = c->list_total + 2 * (nt + 1); } break;
+    case 4: if (pm) { src = c->d_pmask; words = nt + 1 + c->pmask_words + 2 * nt; } break;
+    case 5: if (c->d_tris) { src = c->d_tris; words = (uint64_t)c->ntri * iqpt::kTriFloat4 * 4; } break;
+    case 6: if (c->d_sph) { src = c->d_sph; words = (uint64_t)c->nsph * 4; } break;
+    default: return iqpt::fail(IQPT_ERR_INVALID_ARG, "unknown buffer selector");
+    }
+    *n = words;
+    if (!out || words == 0) return IQPT_OK;
+    if (cap < words) return iqpt::fail(IQPT_ERR_INVALID_ARG, "buffer too small");
+    if (what == 0) std::memcpy(out, grid, sizeof grid);
+    else IQPT_HIP(hipMemcpy(out, src, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return IQPT_OK;
+}
+
 /* Internal (tests/test_gpu_bvh.py): the BVH of the uploaded packet — node count and the number of
  * triangles left on the always-tested list (both 0 without a BVH). */
 int iqpt_debug_bvh_info(iqpt_ctx* c, uint32_t* nnodes, uint32_t* nalways) {

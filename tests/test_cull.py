@@ -5,7 +5,8 @@ kernel's own float operation chain proves that the reference's tests reject it f
 ray of the tile. Here the host build of the same header is checked against the oracle: for random
 cameras, tiles and primitives (many of them straddling the tile's rays), every primitive reported
 culled must be rejected by the oracle's Möller–Trumbore / sphere test for random pixels and jitters
-of the tile — with t_max = FLT_MAX, so only the order-independent tests count. The GPU parity tests
+of the tile and for its corner pixels with the extreme jitters (corner_rays) — with t_max = FLT_MAX,
+so only the order-independent tests count. The GPU parity tests
 then check whole frames rendered with culling against the oracle bit for bit.
 """
 import ctypes as C
@@ -39,6 +40,58 @@ def cull_tile(cam, xa, xb, ya, yb, tris9, sph4):
     return ok == 1, tc.astype(bool), sc.astype(bool)
 
 
+XORWOW_WEYL = 362437
+M32 = 0xffffffff
+
+
+def _solve_xor_shl(a, s):
+    """t with t ^ (t << s) == a (32 bits): bit i of t is a_i ^ t_(i - s)."""
+    t = 0
+    for i in range(32):
+        t |= (((a >> i) ^ ((t >> (i - s)) if i >= s else 0)) & 1) << i
+    return t
+
+
+def _solve_xor_shr(a, s):
+    """v with v ^ (v >> s) == a (32 bits): bit i of v is a_i ^ v_(i + s)."""
+    v = 0
+    for i in reversed(range(32)):
+        v |= (((a >> i) ^ ((v >> (i + s)) if i + s < 32 else 0)) & 1) << i
+    return v
+
+
+def state_with_outputs(r1, r2, rng):
+    """An XORWOW state (v0..v4, d) whose next two outputs are r1 and r2: the step (csrc/iq_xorwow.h) is
+    invertible, so v2, v3, v4 and d are free and v0, v1 follow from the two outputs."""
+    v2, v3, v4, d = (int(q) for q in rng.integers(1, 1 << 32, 4, dtype=np.uint64))
+    w1 = (r1 - d - XORWOW_WEYL) & M32                 # v4 after the first step
+    w2 = (r2 - d - 2 * XORWOW_WEYL) & M32             # v4 after the second
+    v0 = _solve_xor_shr(_solve_xor_shl(w1 ^ v4 ^ ((v4 << 4) & M32), 1), 2)
+    v1 = _solve_xor_shr(_solve_xor_shl(w2 ^ w1 ^ ((w1 << 4) & M32), 1), 2)
+    st = np.array([v0, v1, v2, v3, v4, d], dtype=np.uint32)
+    chk = st.copy()
+    lib = oracle.load()
+    assert lib.iqo_xorwow_next(chk.ctypes.data_as(UP)) == r1 and lib.iqo_xorwow_next(chk.ctypes.data_as(UP)) == r2
+    return st
+
+
+def corner_rays(cam, xa, xb, ya, yb, rng):
+    """The camera rays of the bundle's corner pixels with the four extreme jitter pairs: random::real maps the
+    generator's outputs 0 and 2^32 - 1 to the jitters -0.5 and +0.5 exactly (x from the first draw, y from the
+    second)."""
+    lib = oracle.load()
+    out = []
+    for x, y in sorted({(xa, ya), (xb, ya), (xa, yb), (xb, yb)}):
+        for r1 in (0, M32):
+            for r2 in (0, M32):
+                st = state_with_outputs(r1, r2, rng)
+                o = np.zeros(4, np.float32)
+                d = np.zeros(4, np.float32)
+                lib.iqo_get_ray(C.byref(cam), x, y, st.ctypes.data_as(UP), o.ctypes.data_as(FP), d.ctypes.data_as(FP))
+                out.append((o, d))
+    return out
+
+
 def tile_rays(cam, xa, xb, ya, yb, n, rng):
     lib = oracle.load()
     out = []
@@ -51,10 +104,10 @@ def tile_rays(cam, xa, xb, ya, yb, n, rng):
         lib.iqo_get_ray(C.byref(cam), x, y, st.ctypes.data_as(UP), o.ctypes.data_as(FP), d.ctypes.data_as(FP))
         out.append((o, d))
     # the tile's extreme pixels with the extreme jitter draws (u = 0 and u = 1 come from these states)
-    return out
+    return out + corner_rays(cam, xa, xb, ya, yb, rng)
 
 
-def tri_hit(v0, v1, v2, o, d):
+def tri_hit(v0, v1, v2, o, d, t_max=FLT_MAX):
     lib = oracle.load()
     z = np.zeros(4, np.float32)
     t = C.c_float()
@@ -64,7 +117,7 @@ def tri_hit(v0, v1, v2, o, d):
     a = [np.append(v, np.float32(1)).astype(np.float32) for v in (v0, v1, v2)]
     return lib.iqo_triangle_intersect(a[0].ctypes.data_as(FP), a[1].ctypes.data_as(FP), a[2].ctypes.data_as(FP),
                                       z.ctypes.data_as(FP), z.ctypes.data_as(FP), z.ctypes.data_as(FP),
-                                      o.ctypes.data_as(FP), d.ctypes.data_as(FP), T_MIN, FLT_MAX, C.byref(t),
+                                      o.ctypes.data_as(FP), d.ctypes.data_as(FP), T_MIN, t_max, C.byref(t),
                                       p4.ctypes.data_as(FP), n4.ctypes.data_as(FP), C.byref(front))
 
 

@@ -189,3 +189,129 @@ __device__ __forceinline__ float iq_tanf_bf(float x) {
     y = (j & 2) ? -rc : y;
     return f_sign(x) ? -y : y;
 }
+
+// ---- Lean forms: the forms above restricted to the operand ranges the scatter almost always produces. Each
+// runs, on its stated domain, exactly the IEEE operations of the range the form above selects there, on the same
+// operands in the same order; what is dropped is evaluated above and thrown away (special-case selects, guarded
+// division blocks, sign handling of operands whose sign bit is clear: |v| and a select on f_sign(v) are the
+// identity for them). Outside its domain a lean form's result is unspecified: the caller proves the domain
+// (or_scatter_core: one wave vote on iq_scatter_lean_ok per scatter) or takes the forms above.
+// tests/test_gpu_scatter_lean.py compares each with the form above on its domain, bit for bit.
+
+// Domain test of the atan2 pair for one element: x, y finite and non-zero with |y|, |x| in [2^-62, 2^62] (iq_div's
+// short range; the quotient is then in [2^-124, 2^124], below iq_rcp_guarded's 2^126). NaN fails every compare.
+__device__ __forceinline__ bool iq_atan2_lean_ok(float y, float x) {
+    const float ay = __builtin_fabsf(y), ax = __builtin_fabsf(x);
+    return ay >= 0x1p-62f && ay <= 0x1p62f && ax >= 0x1p-62f && ax <= 0x1p62f;
+}
+// Domain test of the acos pair for one element: x in [+0, 1] (sign bit clear, not NaN): one unsigned compare.
+__device__ __forceinline__ bool iq_acos_lean_ok(float x) { return __float_as_uint(x) <= 0x3f800000u; }
+// Domain test of the trigonometric forms for one element: x in [+0, 8192].
+__device__ __forceinline__ bool iq_trig_lean_ok(float x) { return __float_as_uint(x) <= 0x46000000u; }
+
+// The scatter's per-lane vote: the operands of its two atan2 and its two acos lie in the lean domains. The angles
+// that follow (alpha, beta in [0, pi/2], |phi_i - phi_o| <= 2 pi) are then inside the trigonometric domains by
+// construction.
+__device__ __forceinline__ bool iq_scatter_lean_ok(float wox, float woy, float dx, float dy, float cto, float cti) {
+    return iq_atan2_lean_ok(woy, wox) && iq_atan2_lean_ok(dy, dx) && iq_acos_lean_ok(cto) && iq_acos_lean_ok(cti);
+}
+
+// iq_rcp2 / iq_div_pre2 without v_div_fixup_f32: for finite non-zero operands whose quotient neither overflows nor
+// underflows the fixup returns its first operand with the quotient's sign (iq_fastdiv.h), which it already has.
+// x, b in [2^-124, 2^124]; a = +0 or |a| >= 2^-24 with |a / b| in [2^-125, 2^125].
+__device__ __forceinline__ iq_f2 iq_rcp2_nf(iq_f2 x) {
+    const iq_f2 y0 = {__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)};
+    const iq_f2 e = f2_fma(-x, y0, (iq_f2){1.0f, 1.0f});
+    return f2_fma(e, y0, y0);
+}
+__device__ __forceinline__ iq_f2 iq_div_pre2_nf(iq_f2 a, iq_f2 b, iq_f2 y) {
+    const iq_f2 q = a * y;
+    const iq_f2 r = f2_fma(-b, q, a);
+    return f2_fma(r, y, q);
+}
+
+// iq_atanf2 on x in [2^-124, 2^124]: no |x|, no sign select, no NaN select, no IEEE reciprocal, no fixups (x + 1 is
+// in [1, 2^124]; x - 1 is +0 where x = 1 and at least 2^-24 in magnitude elsewhere, the quotient +0 or >= 2^-25).
+__device__ __forceinline__ iq_f2 iq_atanf2_lean(iq_f2 ax) {
+    const bool b1x = ax.x > 2.414213562373095f, b1y = ax.y > 2.414213562373095f;
+    const bool b2x = ax.x > 0.4142135623730950f, b2y = ax.y > 0.4142135623730950f;
+    const iq_f2 rc = iq_rcp2_nf(ax);
+    const iq_f2 am1 = ax - 1.0f, ap1 = ax + 1.0f;
+    const iq_f2 r2 = iq_div_pre2_nf(am1, ap1, iq_rcp2_nf(ap1));
+    const iq_f2 y0 = {b1x ? IQ_PI_DIV_2 : (b2x ? IQ_PI_DIV_4 : 0.0f), b1y ? IQ_PI_DIV_2 : (b2y ? IQ_PI_DIV_4 : 0.0f)};
+    const iq_f2 r = {b1x ? -rc.x : (b2x ? r2.x : ax.x), b1y ? -rc.y : (b2y ? r2.y : ax.y)};
+    const iq_f2 z = r * r;
+    return y0 + ((((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z
+                  - 3.33329491539e-1f) * z * r + r);
+}
+
+// iq_atan2f2 where iq_atan2_lean_ok holds for both elements: the short division, the arctangent of a positive
+// quotient (in [2^-124, 2^124]: no fixups), the quadrant from the two sign bits.
+__device__ __forceinline__ iq_f2 iq_atan2f2_lean(iq_f2 y, iq_f2 x) {
+    const iq_f2 ay = f2_abs(y), ax = f2_abs(x);
+    const iq_f2 z = iq_atanf2_lean(iq_div_pre2_nf(ay, ax, iq_rcp2_nf(ax)));
+    const iq_f2 res = f2_sel(f_sign(x.x), f_sign(x.y), IQ_PI - z, z);
+    return f2_neg_if(f_sign(y.x), f_sign(y.y), res);
+}
+
+// iq_acosf2 where iq_acos_lean_ok holds for both elements: the ranges x <= 0.5 and x > 0.5 only; asin's argument
+// (x or the root) has its sign bit clear.
+__device__ __forceinline__ iq_f2 iq_acosf2_lean(iq_f2 x) {
+    const bool hix = x.x > 0.5f, hiy = x.y > 0.5f;
+    const iq_f2 s = iq_sqrt_n2(0.5f * (1.0f - x));
+    const iq_f2 a = f2_sel(hix, hiy, s, x);
+    const iq_f2 zz = a * a;
+    const iq_f2 p = ((((4.2163199048e-2f * zz + 2.4181311049e-2f) * zz + 4.5470025998e-2f) * zz
+                      + 7.4953002686e-2f) * zz + 1.6666752422e-1f) * zz * a + a;
+    const iq_f2 as = f2_sel(a.x < 1.0e-4f, a.y < 1.0e-4f, a, p);
+    return f2_sel(hix, hiy, 2.0f * as, IQ_PI_DIV_2 - as);
+}
+
+// iq_sin_cos2 for v.x in [+0, 8192] (the sine's sign comes from the octant alone) and |v.y| <= 8192 (the cosine
+// is even: its argument may be negative), neither NaN: no branch to the scalar functions.
+__device__ __forceinline__ iq_f2 iq_sin_cos2_lean(iq_f2 v) {
+    const iq_f2 ax = {v.x, __builtin_fabsf(v.y)};
+    const iq_f2 jf = IQ_FOPI * ax;
+    int jx = (int)jf.x, jy = (int)jf.y;
+    const iq_f2 y0 = {(float)jx, (float)jy};
+    const iq_f2 y = f2_sel(jx & 1, jy & 1, y0 + 1.0f, y0);
+    jx += jx & 1;
+    jy += jy & 1;
+    const iq_f2 r = ((ax - y * IQ_DP1) - y * IQ_DP2) - y * IQ_DP3;
+    const iq_f2 z = r * r;
+    const iq_f2 sp = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
+    iq_f2 cp = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z;
+    cp = cp - 0.5f * z;
+    cp = cp + 1.0f;
+    const int ox = jx & 7, oy = jy & 7;
+    const int qx = ox & 3, qy = oy & 3;
+    const bool swx = qx == 1 || qx == 2, swy = qy == 1 || qy == 2;
+    const float sx = swx ? cp.x : sp.x;
+    const float cy = swy ? sp.y : cp.y;
+    const bool nsx = ox > 3;
+    const bool ncy = (oy > 3) != (qy > 1);
+    return (iq_f2){nsx ? -sx : sx, ncy ? -cy : cy};
+}
+
+// iq_tanf_bf for x in [+0, 8192]: no |x|, no branch to the scalar function, no final sign select. The 1e-4 select
+// and the guarded reciprocal stay (the reduced argument can be tiny next to an odd multiple of pi/2).
+__device__ __forceinline__ float iq_tanf_lean(float ax) {
+    int j = (int)(IQ_FOPI * ax);
+    float yj = (float)j;
+    if (j & 1) {
+        j += 1;
+        yj += 1.0f;
+    }
+    const float r = ((ax - yj * IQ_DP1) - yj * IQ_DP2) - yj * IQ_DP3;
+    const float zz = r * r;
+    const float p = (((((9.38540185543e-3f * zz + 3.11992232697e-3f) * zz + 2.44301354525e-2f) * zz
+                       + 5.34112807005e-2f) * zz + 1.33387994085e-1f) * zz + 3.33331568548e-1f) * zz * r + r;
+    float y = ax > 1.0e-4f ? p : r;
+    const float ay = __builtin_fabsf(y);
+    float rc = iq_rcp(y);
+    if (__builtin_expect((j & 2) && !(ay >= 0x1p-126f && ay < 0x1p126f), 0)) {
+        asm volatile("" ::: "memory");
+        rc = 1.0f / y;
+    }
+    return (j & 2) ? -rc : y;
+}

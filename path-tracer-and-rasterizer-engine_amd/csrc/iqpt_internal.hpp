@@ -365,7 +365,10 @@ constexpr int kOptPipe = 1 << 21;      // resident scenes: a lane traces its pat
                                        // iteration; its own variants (4 waves/SIMD)
 constexpr int kOptDefault = kOptCamConst | kOptAccTable | kOptPair | kOptSinCos | kOptLB5 | kOptFastDiv | kOptCull |
                             kOptBvh | kOptScatter2;
-constexpr uint32_t kStatsHeader = 24;        // kOptStats: 24 counters, then per-wave (start, end, iterations)
+constexpr uint32_t kStatsHeader = 32;        // kOptStats: 32 counter words, then per-wave (start, end, iterations)
+constexpr uint32_t kStatsLegacyWords = 24;   // the words iqpt_debug_read_stats returns (its callers pass 24-word buffers);
+                                             // words 24.. are read by iqpt_debug_read_stats_ext (24: scatter iterations
+                                             // that took the fallback of the lean transcendental paths)
 constexpr uint32_t kStatsWaveSlots = 65536;
 constexpr uint32_t kStatsQueueSlots = 65536;   // kOptStats: then the s_memrealtime at which queue position q was taken
 constexpr uint32_t kStatsPhaseWords = 4;       // kOptStats: then per wave slot the shader-clock cycles (s_memtime) spent in

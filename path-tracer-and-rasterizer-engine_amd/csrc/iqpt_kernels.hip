@@ -453,9 +453,20 @@ __device__ __forceinline__ void sphere_hit(const float4 sph, float t, const ray3
 // oren_nayar::scatter (material.cu:5-43) at hit point h with hit normal n: writes the continuation
 // ray into r and returns coeff (A + B cos(phi_i - phi_o) sin(alpha) tan(beta)) and q = cos / pdf; the
 // record is att_c * q with att_c = (albedo_c * coeff) * (1 / pi).
-template <int OPT>
+//
+// kOptScatter2 with IQPT_SCATTER_LEAN (the default): once the continuation direction is known every scattering lane
+// checks that the operands of the coefficient's transcendentals lie in the domains of iq_fp2.h's lean forms
+// (iq_scatter_lean_ok), and the wave takes the lean coefficient only if no lane objects; otherwise the whole wave runs
+// the branch-free forms as before. The branch is wave-uniform, the lean forms run the same operations on their
+// domains, so no bit changes (tests/test_gpu_scatter_lean.py). *fell_back (kOptStats) is set on the other path.
+// -DIQPT_SCATTER_LEAN=0 restores the former scatter for A/B builds (iqpt/_build.py SCATTER_FULL_LIB).
+#ifndef IQPT_SCATTER_LEAN
+#define IQPT_SCATTER_LEAN 1
+#endif
+template <int OPT, bool LEAN = (IQPT_SCATTER_LEAN != 0)>
 __device__ __forceinline__ void or_scatter_core(float hx, float hy, float hz, float nx, float ny, float nz, ray3& r,
-                                                rng6& s, float A, float B, float& coeff, float& q) {
+                                                rng6& s, float A, float B, float& coeff, float& q,
+                                                bool* fell_back = nullptr) {
     // onb (onb.h:7-12)
     float wx = nx, wy = ny, wz = nz;
     normalize3<OPT>(wx, wy, wz);
@@ -481,7 +492,8 @@ __device__ __forceinline__ void or_scatter_core(float hx, float hy, float hz, fl
     }
     float sphi, cphi;
     if (OPT & kOptScatter2) {
-        const iq_f2 sc = iq_sin_cos2((iq_f2){phi, phi});
+        // phi = 2 pi u1 with u1 in [0, 1]: inside the lean form's domain by construction
+        const iq_f2 sc = LEAN ? iq_sin_cos2_lean((iq_f2){phi, phi}) : iq_sin_cos2((iq_f2){phi, phi});
         sphi = sc.x;
         cphi = sc.y;
     } else if (OPT & kOptSinCos) {
@@ -510,7 +522,16 @@ __device__ __forceinline__ void or_scatter_core(float hx, float hy, float hz, fl
     const float cosw = iq_fmaxf(0.0f, (nx * dx + ny * dy) + nz * dz);
     const float cto = iq_fmaxf(0.0f, (wox * nx + woy * ny) + woz * nz);
     const float cti = iq_fmaxf(0.0f, (dx * nx + dy * ny) + dz * nz);
-    if (OPT & kOptScatter2) {
+    if ((OPT & kOptScatter2) && LEAN && !__any(!iq_scatter_lean_ok(wox, woy, dx, dy, cto, cti))) {
+        // every scattering lane's operands are ordinary: the lean forms (cto, cti <= 1: no replacement of acos)
+        const iq_f2 ph = iq_atan2f2_lean((iq_f2){woy, dy}, (iq_f2){wox, dx});   // (phi_o, phi_i)
+        const iq_f2 th = iq_acosf2_lean((iq_f2){cto, cti});                     // (theta_o, theta_i)
+        const float alpha = iq_fmaxf(th.y, th.x);
+        const float beta = iq_fminf(th.y, th.x);
+        const iq_f2 sc = iq_sin_cos2_lean((iq_f2){alpha, ph.y - ph.x});
+        coeff = A + B * sc.y * sc.x * iq_tanf_lean(beta);
+    } else if (OPT & kOptScatter2) {
+        if ((OPT & kOptStats) && fell_back) *fell_back = true;
         // the independent transcendentals in packed pairs, branch-free (iq_fp2.h; same bits)
         const iq_f2 ph = iq_atan2f2((iq_f2){woy, dy}, (iq_f2){wox, dx});   // (phi_o, phi_i)
         const iq_f2 th = iq_acosf2((iq_f2){cto, cti});
@@ -543,14 +564,15 @@ __device__ __forceinline__ void or_scatter_core(float hx, float hy, float hz, fl
 // The reference's sphere material oren_nayar(albedo .5, sigma 1) at the closest sphere hit
 // (path_tracer.cu:248, 292): continuation ray into r, returns the record's scalar att * cos / pdf.
 template <int OPT>
-__device__ __forceinline__ float oren_nayar_scatter(const float4 sph, float t, ray3& r, rng6& s) {
+__device__ __forceinline__ float oren_nayar_scatter(const float4 sph, float t, ray3& r, rng6& s,
+                                                    bool* fell_back = nullptr) {
     float hx, hy, hz, nx, ny, nz;
     sphere_hit<OPT>(sph, t, r, hx, hy, hz, nx, ny, nz);
     const float sigma2 = 1.0f * 1.0f;
     const float A = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f);
     const float B = 0.45f * sigma2 / (sigma2 + 0.09f);
     float coeff, q;
-    or_scatter_core<OPT>(hx, hy, hz, nx, ny, nz, r, s, A, B, coeff, q);
+    or_scatter_core<OPT>(hx, hy, hz, nx, ny, nz, r, s, A, B, coeff, q, fell_back);
     const float att = (0.5f * coeff) * (1.0f / IQ_PI);           // m_albedo * coeff / pi
     return att * q;
 }
@@ -1455,6 +1477,8 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                        s_term_lanes = 0;
     // kOptPipe: iterations whose one scatter served both ray a's sphere hits and promoted ray b's
     unsigned long long s_scatter_both = 0;
+    // scatter iterations in which a lane's operands left the lean domains: the wave ran the branch-free forms
+    unsigned long long s_scatter_fb = 0;
     // wave-level triangle / sphere pair tests (culled resident path); [2] kOptPipe: one-ray triangle pair bodies among [0]
     unsigned long long s_tests[3] = {0, 0, 0};
     unsigned long long s_full = 0;            // iterations forced to the full loop (a secondary ray in the wave)
@@ -1912,11 +1936,12 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                 if (sm) ++s_scatter_exec;
                 if ((sm & pm) && (sm & ~pm)) ++s_scatter_both;
             }
+            bool fell_back = false;
             if (scat) {
                 if (OPT & kOptStats) ++s_scatter_lanes;
                 const float* q = reinterpret_cast<const float*>(lds_sph + (size_t)(hidx >> 1) * kSphPairFloat4) +
                                  (hidx & 1u);
-                sL = oren_nayar_scatter<OPT>(make_float4(q[0], q[2], q[4], q[6]), closest, ray, st);
+                sL = oren_nayar_scatter<OPT>(make_float4(q[0], q[2], q[4], q[6]), closest, ray, st, &fell_back);
                 if (depth + 1 >= p.max_depth) {
                     md_end = true;                   // the last record is this scatter (biased, :252)
                 } else {
@@ -1924,6 +1949,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                     ++depth;
                 }
             }
+            if ((OPT & kOptStats) && __any(fell_back)) ++s_scatter_fb;
             // ---- stage 3: the promoted ray b's terminal hits and the scatters that reached max_depth (they drew:
             // no second promotion)
             const bool term_b = md_end || (next && kind != kHitSphere);
@@ -2280,6 +2306,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
 
             // ------------------------------------------------ shade (path_tracer.cu:297-316)
             bool term = false;
+            bool fell_back1 = false;           // kOptStats: this lane's scatter ran on the wave's fallback path
             uint32_t md_end = 0;               // the path ended on a scatter at max_depth (kOptSplit slot count)
             float Lx = 0.0f, Ly = 0.0f, Lz = 0.0f;
             // speculative lanes' rays are counted by the stitch, for the slots on the chain only
@@ -2366,7 +2393,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                         sphr = g_sph_plain[hidx];
                     }
                     save_base();
-                    const float s = oren_nayar_scatter<OPT>(sphr, closest, ray, st);
+                    const float s = oren_nayar_scatter<OPT>(sphr, closest, ray, st, &fell_back1);
                     if (depth + 1 >= p.max_depth) {
                         term = true;                 // the last record is this scatter (biased, :252)
                         md_end = 1;
@@ -2392,6 +2419,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                 }
             }
             if (OPT & kOptStats) {
+                if (__any(fell_back1)) ++s_scatter_fb;
                 if (__ballot(active && kind == kHitSphere)) ++s_scatter_exec;
                 const uint64_t tm = __ballot(term);
                 if (tm) {
@@ -2554,6 +2582,7 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
             atomicAdd(p.stats + 13, s_refill_lanes);
             atomicAdd(p.stats + 22, s_scatter_both);
             atomicAdd(p.stats + 23, s_tests[2]);
+            atomicAdd(p.stats + 24, s_scatter_fb);
         }
         {
             // BVH work and the primitive tests executed, summed over the wave's lanes
@@ -2646,6 +2675,34 @@ __global__ __launch_bounds__(256) void iqpt_libm_kernel(int fn, const float* a, 
         default: v = iq_sqrt_n2(va); break;                   // 19: iq_sqrt_n from .y
         }
         r = hi ? v.y : v.x;
+    }
+    if (fn >= 20 && fn <= 26) {
+        // iq_fp2.h lean forms (tests/test_gpu_scatter_lean.py: against the forms above on the lean domains), paired
+        // with the mirrored index as above: 20 / 21 atan2(a, b) from .x / .y, 22 / 23 acos(a), 24 sin(a) from .x,
+        // 25 cos(a) from .y, 26 tan(a)
+        const uint32_t k = n - 1u - i;
+        const float xk = a[k], yk = b[k];
+        const bool hi = fn & 1;
+        const iq_f2 va = hi ? (iq_f2){xk, x} : (iq_f2){x, xk}, vb = hi ? (iq_f2){yk, y} : (iq_f2){y, yk};
+        iq_f2 v = {0.0f, 0.0f};
+        switch (fn) {
+        case 20: case 21: v = iq_atan2f2_lean(va, vb); break;
+        case 22: case 23: v = iq_acosf2_lean(va); break;
+        case 24: case 25: v = iq_sin_cos2_lean(va); break;
+        default: v = (iq_f2){iq_tanf_lean(x), 0.0f}; break;
+        }
+        r = hi ? v.y : v.x;
+    }
+    if (fn >= 27 && fn <= 30) {
+        // the scatter's per-lane vote (1.0 = lean, 0.0 = objects), the probed operands in one slot and ordinary ones
+        // in the others: 27 (woy, wox) = (a, b), 28 (dy, dx) = (a, b), 29 (cto, cti) = (a, b); 30 the trigonometric
+        // domain test of a
+        const float o = 0.5f;
+        const bool ok = fn == 27 ? iq_scatter_lean_ok(y, x, o, o, o, o)
+                      : fn == 28 ? iq_scatter_lean_ok(o, o, y, x, o, o)
+                      : fn == 29 ? iq_scatter_lean_ok(o, o, o, o, x, y)
+                                 : iq_trig_lean_ok(x);
+        r = ok ? 1.0f : 0.0f;
     }
     out[i] = r;
 }

@@ -3434,6 +3434,8 @@ int iqpt_debug_set_kernel_options(iqpt_ctx* c, int opt) {
         if (hipMalloc(&c->d_stats, words * sizeof(unsigned long long)) != hipSuccess)
             return iqpt::fail(IQPT_ERR_OUT_OF_MEMORY, "stats");
         IQPT_HIP(hipMemset(c->d_stats, 0, words * sizeof(unsigned long long)));
+        // the context's streams do not wait for the null stream: the counters must be clear before a launch adds to them
+        IQPT_HIP(hipDeviceSynchronize());
     }
     c->opt = opt;
     c->opt_fixed = true;
@@ -3693,18 +3695,36 @@ int iqpt_debug_read_wave_times(iqpt_ctx* c, unsigned long long* out, uint32_t ca
     return IQPT_OK;
 }
 
+/* Internal (tools/wave_timeline.py, tests/test_gpu_scatter_lean.py): the counter words after the 24 that
+ * iqpt_debug_read_stats returns (word 24 first), at most cap of them; *n = how many. Does not clear: call before
+ * iqpt_debug_read_stats, which clears every counter word. */
+int iqpt_debug_read_stats_ext(iqpt_ctx* c, unsigned long long* out, uint32_t cap, uint32_t* n) {
+    if (!c || !out || !n) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    *n = 0;
+    int st = enter(c);
+    if (st) return st;
+    IQPT_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t m = std::min<uint32_t>(cap, iqpt::kStatsHeader - iqpt::kStatsLegacyWords);
+    if (!c->d_stats) std::memset(out, 0, m * sizeof(unsigned long long));
+    else IQPT_HIP(hipMemcpy(out, c->d_stats + iqpt::kStatsLegacyWords, m * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost));
+    *n = m;
+    return IQPT_OK;
+}
+
 int iqpt_debug_read_stats(iqpt_ctx* c, unsigned long long* out16) {
-    unsigned long long* out8 = out16;   // kStatsHeader (24) counters (tools/ab_kernel.py)
+    unsigned long long* out8 = out16;   // the first kStatsLegacyWords (24) counters (tools/ab_kernel.py)
     if (!c || !out8) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     int st = enter(c);
     if (st) return st;
     IQPT_HIP(hipStreamSynchronize(c->stream));
     if (!c->d_stats) {
-        std::memset(out8, 0, iqpt::kStatsHeader * sizeof(unsigned long long));
+        std::memset(out8, 0, iqpt::kStatsLegacyWords * sizeof(unsigned long long));
         return IQPT_OK;
     }
-    IQPT_HIP(hipMemcpy(out8, c->d_stats, iqpt::kStatsHeader * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    IQPT_HIP(hipMemcpy(out8, c->d_stats, iqpt::kStatsLegacyWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     IQPT_HIP(hipMemset(c->d_stats, 0, iqpt::kStatsHeader * sizeof(unsigned long long)));   // counters, wave slot index
+    IQPT_HIP(hipDeviceSynchronize());   // before the next launch on the context's (non-blocking) streams adds to them
     return IQPT_OK;
 }
 

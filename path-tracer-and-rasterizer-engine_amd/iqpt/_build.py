@@ -57,11 +57,25 @@ LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tra
                "svgf/iq_svgf_kernels.hip", "svgf/iq_svgf.cpp"]
 
 
-def _run(cmd: list[str], cwd: Path | None = None) -> None:
+def _run(cmd: list[str], cwd: Path | None = None, stderr_to: Path | None = None) -> None:
     proc = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True)
     if proc.returncode != 0:
         raise RuntimeError(f"build failed ({proc.returncode}): {' '.join(map(str, cmd))}\n"
                            f"{proc.stdout}\n{proc.stderr}")
+    if stderr_to is not None:
+        stderr_to.write_text(proc.stderr)
+
+
+KERNELS_SOURCE = "iqpt_kernels.hip"
+REMARKS_FLAG = "-Rpass-analysis=kernel-resource-usage"
+
+
+def _build_dir(target: Path, stats: bool, flags: bool) -> Path:
+    return BUILD_DIR / (target.stem if flags else ("stats" if stats else "prod"))
+
+
+def _remarks_path(bdir: Path) -> Path:
+    return bdir / (KERNELS_SOURCE + ".remarks.txt")
 
 
 def _newer(target: Path, deps: list[Path]) -> bool:
@@ -117,7 +131,7 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
     srcs = [CSRC / s for s in LIB_SOURCES]
     if not force and _newer(target, srcs + _deps() + [Path(__file__)]):
         return target
-    bdir = BUILD_DIR / (target.stem if flags else ("stats" if stats else "prod"))
+    bdir = _build_dir(target, stats, bool(flags))
     bdir.mkdir(parents=True, exist_ok=True)
     objs = []
     cmds = []
@@ -126,11 +140,13 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
         o = bdir / (s.name + ".o")
         # an object is rebuilt when its source, a header or this recipe is newer (force: always)
         if force or not _newer(o, [s] + _deps() + [Path(__file__)]):
-            cmds.append([HIPCC, *HIP_FLAGS, *extra, "-x", "hip", "-c", str(s), "-o", str(o)])
+            cmd = [HIPCC, *HIP_FLAGS, *extra, "-x", "hip", "-c", str(s), "-o", str(o)]
+            # the path-tracing kernels' resource remarks are kept beside the object (kernel_resources)
+            cmds.append((cmd + [REMARKS_FLAG], _remarks_path(bdir)) if s.name == KERNELS_SOURCE else (cmd, None))
         objs.append(o)
     if cmds:
         with ThreadPoolExecutor(max_workers=min(4, len(cmds))) as ex:
-            list(ex.map(_run, cmds))
+            list(ex.map(lambda c: _run(c[0], stderr_to=c[1]), cmds))
     tmp = target.with_suffix(".so.tmp")
     _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", *map(str, objs), "-o", str(tmp)])
     os.replace(tmp, target)
@@ -214,6 +230,39 @@ def build_pair_body_libs(force: bool = False) -> list[Path]:
         return list(ex.map(lambda kw: build_lib(force, **kw), jobs))
 
 
+# The Oren–Nayar scatter on the branch-free transcendental pairs alone (the form before the wave vote for the lean
+# paths): an A/B library for bench.py --lib and the tools' --lib, and the other side of
+# tests/test_gpu_scatter_lean.py. The instrumented form of it is built on demand (build_lib with these flags).
+SCATTER_FULL_FLAGS = ("-DIQPT_SCATTER_LEAN=0",)
+SCATTER_FULL_LIB = PKG_DIR / "libiqpt_scatterfull.so"
+SCATTER_FULL_STATS_LIB = PKG_DIR / "libiqpt_stats_scatterfull.so"
+
+
+def build_scatter_libs(force: bool = False) -> list[Path]:
+    """The library tests/test_gpu_scatter_lean.py compares the default one with (measurement and test only)."""
+    return [build_lib(force, flags=SCATTER_FULL_FLAGS, target=SCATTER_FULL_LIB)]
+
+
+def kernel_resources(target: Path = LIB_PATH, stats: bool = False) -> dict[str, dict[str, int]]:
+    """Per kernel of iqpt_kernels.hip as compiled into `target` (a library build_lib has built): the compiler's
+    resource remarks (-Rpass-analysis=kernel-resource-usage, kept beside the object), as
+    {mangled name: {"VGPRs": .., "ScratchSize [bytes/lane]": .., "SGPRs Spill": .., "Occupancy [waves/SIMD]": ..}}."""
+    import re
+    text = _remarks_path(_build_dir(target, stats, flags=target not in (LIB_PATH, STATS_LIB_PATH))).read_text()
+    out: dict[str, dict[str, int]] = {}
+    name = None
+    for line in text.splitlines():
+        m = re.search(r"remark: .*Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            out[name] = {}
+            continue
+        m = re.search(r"remark: [^\[]*?\s{2,}([A-Za-z][^:]*): (\d+)", line)
+        if m and name:
+            out[name][m.group(1).strip()] = int(m.group(2))
+    return out
+
+
 def build_ref(force: bool = False) -> Path | None:
     """TEST INFRASTRUCTURE: the reference's own source as a host library (oracle/ref/build_ref.py), into the
     git-ignored oracle/_ref/. None, quietly, where the reference directory or a compiler is absent: the build is
@@ -234,7 +283,8 @@ def build_all(force: bool = False) -> None:
     build_tools(force)
     build_oracle(force)
     build_ref(force)
-    build_pair_body_libs(force)
+    with ThreadPoolExecutor(max_workers=2) as ex:
+        list(ex.map(lambda f: f(force), (build_pair_body_libs, build_scatter_libs)))
 
 
 if __name__ == "__main__":

@@ -84,6 +84,12 @@ ph = (C.c_ulonglong * (4 * cap))()
 lb.iqpt_debug_read_wave_phases.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint32]
 _lib.check(lb.iqpt_debug_read_wave_phases(pt._h, ph, cap), "wave phases")
 phases = np.array(ph[:4 * nw.value], dtype=np.float64).reshape(-1, 4)
+# the counter words past the first 24 (word 24: scatter iterations on the fallback of the lean transcendental paths);
+# a library from before them has no such call
+ext = (C.c_ulonglong * 8)()
+if hasattr(lb, "iqpt_debug_read_stats_ext"):
+    lb.iqpt_debug_read_stats_ext.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint32, C.POINTER(C.c_uint32)]
+    _lib.check(lb.iqpt_debug_read_stats_ext(pt._h, ext, 8, C.byref(C.c_uint32(0))), "stats ext")
 lb.iqpt_debug_read_stats(pt._h, s)
 v = [int(x) for x in s]
 t, k = pt.kernel_time()
@@ -110,6 +116,9 @@ res = {"config": args.config, "spp": spp, "two_ray": args.two_ray, "overlap": ar
        "scatter_iteration_frac": round(v[3] / max(v[0], 1), 3),
        # two-ray kernel: iterations whose one scatter served ray a's sphere hits and promoted ray b's together
        "scatter_both_iteration_frac": round(v[22] / max(v[0], 1), 3), "scatter_lanes_per_scatter_iteration": round(v[4] / max(v[3], 1), 2),
+       # scatter iterations (word 3) and those among them in which a lane's operands left the lean domains, so the
+       # wave ran the branch-free transcendental forms (word 24)
+       "scatter_iterations": v[3], "scatter_fallback_iterations": int(ext[0]),
        # two-ray kernel: triangle pairs visited (word 8) and those that ran the one-ray body (word 23: ray b did not
        # need the pair); the rest ran the two-ray body
        "tri_pairs_visited": v[8], "tri_pair_one_ray_bodies": v[23], "tri_pair_two_ray_bodies": v[8] - v[23],

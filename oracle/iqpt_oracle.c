@@ -653,6 +653,37 @@ int iqo_oren_nayar(const float* p4, const float* n4, const float* din4, uint32_t
     state6[5] = s.d;
     return ret;
 }
+/* n Oren-Nayar scatters of a material (albedo4, roughness sigma, clamped as the constructor does), case i from
+ * p4 / n4 / din4 / state6 at stride 4 / 4 / 4 / 6: the same oren_nayar_scatter as iqo_oren_nayar, whose record it
+ * gives for sigma 1 and albedo (.5, .5, .5, 0) (tests/test_scatter_probe_cases.py). */
+void iqo_oren_nayar_batch(int64_t n, float sigma, const float* albedo4, const float* p4, const float* n4,
+                          const float* din4, uint32_t* state6, float* att4, float* pdf, float* cosw, float* ro4,
+                          float* rd4) {
+    for (int64_t i = 0; i < n; ++i) {
+        ray_t rin, rout;
+        memset(&rin, 0, sizeof rin);
+        memcpy(&rin.d, din4 + 4 * i, 16);
+        hit_record hr;
+        memset(&hr, 0, sizeof hr);
+        memcpy(&hr.p, p4 + 4 * i, 16);
+        memcpy(&hr.n, n4 + 4 * i, 16);
+        hr.mat = MAT_OREN_NAYAR;
+        memcpy(&hr.albedo, albedo4, 16);
+        hr.param = clamp_sigma(sigma);
+        iq_xorwow_state s;
+        for (int q = 0; q < 5; ++q) s.v[q] = state6[6 * i + q];
+        s.d = state6[6 * i + 5];
+        scatter_record sr;
+        oren_nayar_scatter(&rin, &hr, &sr, &rout, &s);
+        memcpy(att4 + 4 * i, &sr.attenuation, 16);
+        pdf[i] = sr.pdf_val;
+        cosw[i] = sr.cos_law_weight;
+        memcpy(ro4 + 4 * i, &rout.o, 16);
+        memcpy(rd4 + 4 * i, &rout.d, 16);
+        for (int q = 0; q < 5; ++q) state6[6 * i + q] = s.v[q];
+        state6[6 * i + 5] = s.d;
+    }
+}
 void iqo_normal_matrix(const float* transform16, float* out16) {
     mat3 s = store3x3((const mat4*)transform16);
     mat3 t = mat3_transposed(&s);

@@ -60,6 +60,8 @@ def load(glibc: bool = False, flavour: str | None = None) -> C.CDLL:
     lib.iqo_onb.argtypes = [_FP, _FP, _FP, _FP]
     lib.iqo_cosine_weighted.argtypes = [_UP, _FP]
     lib.iqo_oren_nayar.argtypes = [_FP, _FP, _FP, _UP, _FP, _FP, _FP, _FP, _FP]
+    lib.iqo_oren_nayar_batch.argtypes = [C.c_int64, C.c_float, _FP, _FP, _FP, _FP, _UP, _FP, _FP, _FP, _FP, _FP]
+    lib.iqo_oren_nayar_batch.restype = None
     lib.iqo_real.argtypes = [_UP, C.c_float, C.c_float]
     lib.iqo_real.restype = C.c_float
     lib.iqo_emissive.argtypes = [_FP, _FP, _FP]

@@ -409,6 +409,21 @@ int launch_camera_probe(void* stream, const kparams& p, const float* ndc, float*
 int launch_lds_poison(void* stream, uint32_t pattern, uint32_t lds_bytes, uint32_t blocks);
 // Device probe of the shared math (iqpt_debug_libm).
 int launch_libm(void* stream, int fn, const float* a, const float* b, float* out, uint32_t n);
+// Device probe of the Oren–Nayar scatter (iqpt_debug_scatter; the layouts are stated at iqpt_scatter_probe_kernel).
+struct kscatter_probe {
+    const float* in;          // 12 floats per case
+    const uint32_t* st_in;    // 6 words per case
+    const uint8_t* active;
+    float* ray;               // 6 floats per case
+    float* vals;              // 3 floats per case
+    uint32_t* st_out;         // 6 words per case
+    uint8_t* fell_back;
+    uint32_t n;
+    float A, B, albedo;
+};
+// form: 0 kOptScatter2 | kOptSinCos | kOptFastDiv lean, 1 the same on the branch-free forms, 2 / 3 these two without
+// kOptFastDiv, 4 the plain transliteration (none of the three bits; no sphere mode). hipErrorInvalidValue otherwise.
+int launch_scatter_probe(void* stream, int form, bool sphere, const kscatter_probe& k);
 // grid_blocks = persistent grid size; lds_bytes dynamic LDS; stream = hipStream_t; opt = kOpt* mask.
 int launch_render(void* stream, const kparams& p, uint32_t grid_blocks, uint32_t lds_bytes, bool stream_batches,
                   int opt);

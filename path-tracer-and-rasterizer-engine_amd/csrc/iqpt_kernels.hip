@@ -563,7 +563,7 @@ __device__ __forceinline__ void or_scatter_core(float hx, float hy, float hz, fl
 
 // The reference's sphere material oren_nayar(albedo .5, sigma 1) at the closest sphere hit
 // (path_tracer.cu:248, 292): continuation ray into r, returns the record's scalar att * cos / pdf.
-template <int OPT>
+template <int OPT, bool LEAN = (IQPT_SCATTER_LEAN != 0)>
 __device__ __forceinline__ float oren_nayar_scatter(const float4 sph, float t, ray3& r, rng6& s,
                                                     bool* fell_back = nullptr) {
     float hx, hy, hz, nx, ny, nz;
@@ -572,7 +572,7 @@ __device__ __forceinline__ float oren_nayar_scatter(const float4 sph, float t, r
     const float A = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f);
     const float B = 0.45f * sigma2 / (sigma2 + 0.09f);
     float coeff, q;
-    or_scatter_core<OPT>(hx, hy, hz, nx, ny, nz, r, s, A, B, coeff, q, fell_back);
+    or_scatter_core<OPT, LEAN>(hx, hy, hz, nx, ny, nz, r, s, A, B, coeff, q, fell_back);
     const float att = (0.5f * coeff) * (1.0f / IQ_PI);           // m_albedo * coeff / pi
     return att * q;
 }
@@ -2707,6 +2707,48 @@ __global__ __launch_bounds__(256) void iqpt_libm_kernel(int fn, const float* a, 
     out[i] = r;
 }
 
+// Scatter probe (iqpt_debug_scatter, tests/test_gpu_scatter_probe.py): one Oren–Nayar scatter per case, called
+// exactly as the render kernels call it. Test only. Case i is thread i of a grid of 256-thread blocks, i.e. lane
+// i % 64 of wave i / 64: the test places its cases in waves by this mapping. An inactive case (active[i] == 0) skips
+// the call inside the branch below, so it is diverged, not exited, when its wave votes in or_scatter_core; it writes
+// nothing (the host pre-fills the outputs with a sentinel).
+// OPT carries kOptStats only so that *fell_back is reported: the bit changes nothing else inside or_scatter_core.
+// SPHERE = false: in = hit point (3), hit normal (3), incoming direction (3), 3 unused; or_scatter_core<OPT, LEAN>;
+//   vals = (coeff, q, att) with att = (albedo * coeff) * (1 / pi), the expression of both call sites.
+// SPHERE = true: in = sphere (centre, radius), ray origin (3), direction (3), t, 1 unused; sphere_hit and the scatter
+//   through oren_nayar_scatter<OPT, LEAN> (sigma 1, albedo .5); vals[0] = the record's scalar att * q.
+// Both write the continuation ray (6 floats), the six state words after the call and the fell_back byte.
+template <int OPT, bool LEAN, bool SPHERE>
+__global__ __launch_bounds__(256) void iqpt_scatter_probe_kernel(const kscatter_probe k) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= k.n) return;
+    if (k.active[i]) {
+        const float* in = k.in + 12 * (size_t)i;
+        const uint32_t* w = k.st_in + 6 * (size_t)i;
+        rng6 st = {w[0], w[1], w[2], w[3], w[4], w[5]};
+        bool fell_back = false;
+        ray3 r;
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        if (SPHERE) {
+            r = {in[4], in[5], in[6], in[7], in[8], in[9]};
+            v[0] = oren_nayar_scatter<OPT, LEAN>(make_float4(in[0], in[1], in[2], in[3]), in[10], r, st, &fell_back);
+        } else {
+            r = {0.0f, 0.0f, 0.0f, in[6], in[7], in[8]};
+            or_scatter_core<OPT, LEAN>(in[0], in[1], in[2], in[3], in[4], in[5], r, st, k.A, k.B, v[0], v[1],
+                                       &fell_back);
+            v[2] = (k.albedo * v[0]) * (1.0f / IQ_PI);
+        }
+        const float ro[6] = {r.ox, r.oy, r.oz, r.dx, r.dy, r.dz};
+        const uint32_t so[6] = {st.v0, st.v1, st.v2, st.v3, st.v4, st.d};
+        for (int c = 0; c < 6; ++c) {
+            k.ray[6 * (size_t)i + c] = ro[c];
+            k.st_out[6 * (size_t)i + c] = so[c];
+        }
+        for (int c = 0; c < (SPHERE ? 1 : 3); ++c) k.vals[3 * (size_t)i + c] = v[c];
+        k.fell_back[i] = fell_back ? 1 : 0;
+    }
+}
+
 // Camera probe (tests/test_gpu_camera.py): the general transform and kOptCamAxis's short one for n
 // given (x_ndc, y_ndc), ray components written as 6 floats each (bits compared by the test).
 __global__ __launch_bounds__(256) void iqpt_camera_probe_kernel(const kparams p, const float* ndc, float* gen,
@@ -4357,6 +4399,29 @@ int launch_lds_poison(void* stream, uint32_t pattern, uint32_t lds_bytes, uint32
 int launch_libm(void* stream, int fn, const float* a, const float* b, float* out, uint32_t n) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(iqpt_libm_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, fn, a, b, out, n);
+    return (int)hipGetLastError();
+}
+
+template <int OPT, bool LEAN>
+static void launch_scatter_probe_form(hipStream_t stream, bool sphere, const kscatter_probe& k) {
+    const dim3 grid((k.n + 255) / 256), block(256);
+    if (sphere) hipLaunchKernelGGL((iqpt_scatter_probe_kernel<OPT | kOptStats, LEAN, true>), grid, block, 0, stream, k);
+    else hipLaunchKernelGGL((iqpt_scatter_probe_kernel<OPT | kOptStats, LEAN, false>), grid, block, 0, stream, k);
+}
+
+int launch_scatter_probe(void* stream, int form, bool sphere, const kscatter_probe& k) {
+    if (form < 0 || form > 4 || (form == 4 && sphere)) return (int)hipErrorInvalidValue;
+    if (k.n == 0) return 0;
+    constexpr int kFast = kOptScatter2 | kOptSinCos | kOptFastDiv, kIeee = kOptScatter2 | kOptSinCos;
+    hipStream_t s = (hipStream_t)stream;
+    switch (form) {
+    case 0: launch_scatter_probe_form<kFast, true>(s, sphere, k); break;
+    case 1: launch_scatter_probe_form<kFast, false>(s, sphere, k); break;
+    case 2: launch_scatter_probe_form<kIeee, true>(s, sphere, k); break;
+    case 3: launch_scatter_probe_form<kIeee, false>(s, sphere, k); break;
+    default: hipLaunchKernelGGL((iqpt_scatter_probe_kernel<kOptStats, false, false>), dim3((k.n + 255) / 256),
+                                dim3(256), 0, s, k);
+    }
     return (int)hipGetLastError();
 }
 

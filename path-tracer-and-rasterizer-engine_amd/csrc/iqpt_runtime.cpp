@@ -3602,6 +3602,51 @@ int iqpt_debug_libm(int fn, const float* a, const float* b, float* out, uint64_t
     return st;
 }
 
+/* Internal (tests/test_gpu_scatter_probe.py): n Oren-Nayar scatters on the current device (synchronous), one per
+ * case, by the form `form` of or_scatter_core (0-4, iqpt_internal.hpp launch_scatter_probe); sphere != 0 runs
+ * sphere_hit and oren_nayar_scatter instead (forms 0-3; A, B and albedo unused). in: 12 floats per case, states: 6
+ * words, active: 1 byte (layouts at iqpt_scatter_probe_kernel). ray (6 floats), vals (3 floats), states_out (6 words)
+ * and fell_back (1 byte) per case go to the device as the caller filled them and come back: what an inactive case
+ * holds afterwards is what the caller put there. */
+int iqpt_debug_scatter(int form, int sphere, float A, float B, float albedo, const float* in, const uint32_t* states,
+                       const uint8_t* active, uint64_t n, float* ray, float* vals, uint32_t* states_out,
+                       uint8_t* fell_back) {
+    if (!in || !states || !active || !ray || !vals || !states_out || !fell_back)
+        return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    if (form < 0 || form > 4 || (form == 4 && sphere)) return iqpt::fail(IQPT_ERR_INVALID_ARG, "no such scatter form");
+    if (n == 0) return IQPT_OK;
+    if (n > (1ull << 24)) return iqpt::fail(IQPT_ERR_INVALID_ARG, "n too large");
+    const size_t sizes[7] = {n * 12 * sizeof(float), n * 6 * sizeof(uint32_t), n, n * 6 * sizeof(float),
+                             n * 3 * sizeof(float), n * 6 * sizeof(uint32_t), n};
+    const void* src[7] = {in, states, active, ray, vals, states_out, fell_back};
+    void* back[7] = {nullptr, nullptr, nullptr, ray, vals, states_out, fell_back};
+    void* dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int st = IQPT_OK;
+    for (int i = 0; i < 7 && st == IQPT_OK; ++i)
+        if (hipMalloc(&dev[i], sizes[i]) != hipSuccess) st = iqpt::fail(IQPT_ERR_OUT_OF_MEMORY, "scatter probe buffers");
+    if (st == IQPT_OK) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipMemcpy(dev[i], src[i], sizes[i], hipMemcpyHostToDevice);
+        iqpt::kscatter_probe k;
+        k.in = (const float*)dev[0];
+        k.st_in = (const uint32_t*)dev[1];
+        k.active = (const uint8_t*)dev[2];
+        k.ray = (float*)dev[3];
+        k.vals = (float*)dev[4];
+        k.st_out = (uint32_t*)dev[5];
+        k.fell_back = (uint8_t*)dev[6];
+        k.n = (uint32_t)n;
+        k.A = A;
+        k.B = B;
+        k.albedo = albedo;
+        if (e == hipSuccess) e = (hipError_t)iqpt::launch_scatter_probe(nullptr, form, sphere != 0, k);
+        for (int i = 3; i < 7 && e == hipSuccess; ++i) e = hipMemcpy(back[i], dev[i], sizes[i], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = iqpt::hip_fail(e, "scatter probe");
+    }
+    for (int i = 0; i < 7; ++i) (void)hipFree(dev[i]);
+    return st;
+}
+
 /* Internal (tests/test_camera_axis.py): 1 if the camera qualifies for the short pitch-only transform
  * (kOptCamAxis), its 16 launch constants in k16; 0 otherwise. Host only. */
 int iqpt_debug_cam_axis(const iqpt_camera* cam, float* k16) {

@@ -8,9 +8,6 @@
 
 namespace iqd {
 
-constexpr int kBlockX = 32;   // lanes run along x: every tap of a wave is two coalesced 512-byte row reads
-constexpr int kBlockY = 8;
-
 struct level_params {
     uint32_t width, height;
     int32_t step;             // 2^i
@@ -19,11 +16,10 @@ struct level_params {
     float colour_scale;       // k_i = RN(s_c s_c) 4^i
 };
 
-// launchers (iq_denoise_kernels.hip); each enqueues on `s` and returns the launch status.
+// launcher (iq_denoise_kernels.hip); enqueues on `s` and returns the launch status. levels = 0 is
+// iqp::launch_encode alone.
 // One à-trous level: out = c_{i+1} of in = c_i under the guides; bgra (may be NULL) also gets the encoded frame.
 hipError_t launch_level(hipStream_t s, const level_params& p, const void* in, const void* normal_z, const uint32_t* id,
                         void* out, uint32_t* bgra);
-// The BGRA8 encoding alone (levels = 0).
-hipError_t launch_encode(hipStream_t s, uint32_t width, uint32_t height, const void* in, uint32_t* bgra);
 
 }  // namespace iqd

@@ -23,6 +23,7 @@
 #include "iq_xorwow.h"
 #include "iqpt.h"
 #include "iqpt_internal.hpp"
+#include "post/iq_post.hpp"
 
 namespace iqpt {
 
@@ -59,10 +60,11 @@ const std::vector<uint32_t>& xorwow_tables() {
     return g_tables;
 }
 
+}  // namespace
+
 int hip_fail(hipError_t e, const char* what) {
     return fail(IQPT_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
 }
-}  // namespace
 
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 int fail(int status, const std::string& msg) {
@@ -71,12 +73,6 @@ int fail(int status, const std::string& msg) {
 }
 
 }  // namespace iqpt
-
-#define IQPT_HIP(call)                                                  \
-    do {                                                                \
-        hipError_t e_ = (call);                                         \
-        if (e_ != hipSuccess) return iqpt::hip_fail(e_, #call);         \
-    } while (0)
 
 using iqpt::float4_storage;
 

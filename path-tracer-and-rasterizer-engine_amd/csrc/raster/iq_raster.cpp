@@ -5,25 +5,14 @@
 
 #include <algorithm>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "iq_host_math.hpp"
-#include "iqpt_internal.hpp"
+#include "post/iq_post.hpp"
 #include "raster/iq_raster.hpp"
 #include "raster/iqpt_raster.h"
 
 namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-    return iqpt::fail(IQPT_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
-}
-
-#define IQR_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);    \
-    } while (0)
 
 // a device buffer that only grows
 struct dbuf {
@@ -97,19 +86,19 @@ struct iqpt_raster {
 namespace {
 
 int set_device(iqpt_raster* r) {
-    IQR_HIP(hipSetDevice(r->device));
+    IQPT_HIP(hipSetDevice(r->device));
     return IQPT_OK;
 }
 
 int collect(iqpt_raster* r) {
     if (!r->pending) return IQPT_OK;
-    IQR_HIP(hipEventSynchronize(r->ev[kEvents - 1]));
+    IQPT_HIP(hipEventSynchronize(r->ev[kEvents - 1]));
     float ms = 0.0f;
     for (int k = 0; k < 5; ++k) {
-        IQR_HIP(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
+        IQPT_HIP(hipEventElapsedTime(&ms, r->ev[k], r->ev[k + 1]));
         r->stage_ms[k] += ms;
     }
-    IQR_HIP(hipEventElapsedTime(&ms, r->ev[0], r->ev[kEvents - 1]));
+    IQPT_HIP(hipEventElapsedTime(&ms, r->ev[0], r->ev[kEvents - 1]));
     r->total_ms += ms;
     r->draws += 1;
     r->pending = false;
@@ -119,17 +108,17 @@ int collect(iqpt_raster* r) {
 // the same for the last G-buffer pass
 int collect_guide(iqpt_raster* r) {
     if (!r->guide_pending) return IQPT_OK;
-    IQR_HIP(hipEventSynchronize(r->guide_ev[1]));
+    IQPT_HIP(hipEventSynchronize(r->guide_ev[1]));
     float ms = 0.0f;
-    IQR_HIP(hipEventElapsedTime(&ms, r->guide_ev[0], r->guide_ev[1]));
+    IQPT_HIP(hipEventElapsedTime(&ms, r->guide_ev[0], r->guide_ev[1]));
     r->guide_ms += ms;
     r->guide_pending = false;
     return IQPT_OK;
 }
 
 int upload(dbuf& b, const void* src, size_t bytes, hipStream_t s) {
-    IQR_HIP(b.reserve(std::max<size_t>(bytes, 16)));
-    if (bytes) IQR_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    IQPT_HIP(b.reserve(std::max<size_t>(bytes, 16)));
+    if (bytes) IQPT_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
     return IQPT_OK;
 }
 
@@ -146,14 +135,14 @@ int build_lists(iqpt_raster* r, geometry& g, const iqr::frame_params& fp, bool g
     if (g.ntris) {
         size_t cap = std::max<size_t>(l.recs.bytes / sizeof(iqr::setup_rec), 1024);
         for (int attempt = 0;; ++attempt) {
-            IQR_HIP(l.recs.reserve(cap * sizeof(iqr::setup_rec)));
-            IQR_HIP(hipMemsetAsync(r->cnt.p, 0, sizeof(iqr::counters), s));
-            IQR_HIP((guide ? iqr::launch_setup_guide : iqr::launch_setup)(
+            IQPT_HIP(l.recs.reserve(cap * sizeof(iqr::setup_rec)));
+            IQPT_HIP(hipMemsetAsync(r->cnt.p, 0, sizeof(iqr::counters), s));
+            IQPT_HIP((guide ? iqr::launch_setup_guide : iqr::launch_setup)(
                 s, fp, g.draws.as<iqr::draw_rec>(), g.ndraws, g.tend.as<uint32_t>(), g.ntris, g.indices.as<uint32_t>(),
                 g.clip.as<float>(), g.wn.as<float>(), l.recs.as<iqr::setup_rec>(),
                 (uint32_t)std::min<size_t>(cap, 0xffffffffu), r->cnt.as<iqr::counters>()));
-            IQR_HIP(hipMemcpyAsync(r->host_cnt, r->cnt.p, sizeof(iqr::counters), hipMemcpyDeviceToHost, s));
-            IQR_HIP(hipStreamSynchronize(s));
+            IQPT_HIP(hipMemcpyAsync(r->host_cnt, r->cnt.p, sizeof(iqr::counters), hipMemcpyDeviceToHost, s));
+            IQPT_HIP(hipStreamSynchronize(s));
             if (r->host_cnt->npairs >= 0xffffffffull || r->host_cnt->nrec >= 0xffffffffull)
                 return iqpt::fail(IQPT_ERR_UNSUPPORTED, "more than 2^32 (tile, triangle) pairs in one frame");
             if (r->host_cnt->nrec <= cap) break;
@@ -163,7 +152,7 @@ int build_lists(iqpt_raster* r, geometry& g, const iqr::frame_params& fp, bool g
         nrec = (uint32_t)r->host_cnt->nrec;
         npairs = (uint32_t)r->host_cnt->npairs;
     }
-    if (ev) IQR_HIP(hipEventRecord(ev[0], s));
+    if (ev) IQPT_HIP(hipEventRecord(ev[0], s));
 
     const int in = 0, out = 1;
     // sort key: tile << key_bits | (submission index << 3 | piece), key_bits just wide enough for this draw
@@ -171,28 +160,28 @@ int build_lists(iqpt_raster* r, geometry& g, const iqr::frame_params& fp, bool g
     while ((1ull << key_bits) < ((unsigned long long)nsub << iqr::kPieceBits)) ++key_bits;
     if (npairs) {
         for (int k = 0; k < 2; ++k) {
-            IQR_HIP(l.keys[k].reserve((size_t)npairs * sizeof(unsigned long long)));
-            IQR_HIP(l.vals[k].reserve((size_t)npairs * sizeof(uint32_t)));
+            IQPT_HIP(l.keys[k].reserve((size_t)npairs * sizeof(unsigned long long)));
+            IQPT_HIP(l.vals[k].reserve((size_t)npairs * sizeof(uint32_t)));
         }
-        IQR_HIP(iqr::launch_bin(s, fp, l.recs.as<iqr::setup_rec>(), nrec, key_bits, l.keys[in].as<unsigned long long>(),
+        IQPT_HIP(iqr::launch_bin(s, fp, l.recs.as<iqr::setup_rec>(), nrec, key_bits, l.keys[in].as<unsigned long long>(),
                                 l.vals[in].as<uint32_t>()));
     }
-    if (ev) IQR_HIP(hipEventRecord(ev[1], s));
+    if (ev) IQPT_HIP(hipEventRecord(ev[1], s));
     if (npairs) {
         unsigned tile_bits = 1;
         while ((1ull << tile_bits) < (unsigned long long)fp.ntx * fp.nty) ++tile_bits;
         const unsigned end_bit = key_bits + tile_bits;
         size_t need = 0;
-        IQR_HIP(iqr::sort_pairs(s, nullptr, need, l.keys[in].as<unsigned long long>(),
+        IQPT_HIP(iqr::sort_pairs(s, nullptr, need, l.keys[in].as<unsigned long long>(),
                                 l.keys[out].as<unsigned long long>(), l.vals[in].as<uint32_t>(),
                                 l.vals[out].as<uint32_t>(), npairs, end_bit));
-        IQR_HIP(r->sort_temp.reserve(std::max<size_t>(need, 16)));
+        IQPT_HIP(r->sort_temp.reserve(std::max<size_t>(need, 16)));
         need = r->sort_temp.bytes;
-        IQR_HIP(iqr::sort_pairs(s, r->sort_temp.p, need, l.keys[in].as<unsigned long long>(),
+        IQPT_HIP(iqr::sort_pairs(s, r->sort_temp.p, need, l.keys[in].as<unsigned long long>(),
                                 l.keys[out].as<unsigned long long>(), l.vals[in].as<uint32_t>(),
                                 l.vals[out].as<uint32_t>(), npairs, end_bit));
     }
-    IQR_HIP(iqr::launch_ranges(s, fp, l.keys[out].as<unsigned long long>(), npairs, key_bits, l.ranges.as<uint32_t>()));
+    IQPT_HIP(iqr::launch_ranges(s, fp, l.keys[out].as<unsigned long long>(), npairs, key_bits, l.ranges.as<uint32_t>()));
     return IQPT_OK;
 }
 
@@ -201,22 +190,22 @@ int run_draw(iqpt_raster* r, geometry& g, bool vertex_stage) {
     if (int st = collect(r)) return st;
     hipStream_t s = r->stream;
     const iqr::frame_params& fp = r->fp;
-    IQR_HIP(hipEventRecord(r->ev[0], s));
+    IQPT_HIP(hipEventRecord(r->ev[0], s));
     if (vertex_stage && !g.transformed) {
-        IQR_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
+        IQPT_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
                                    g.mesh_verts.as<float>(), r->camera.as<float>(), r->camera.as<float>() + 16,
                                    g.clip.as<float>(), g.wn.as<float>()));
         g.transformed = true;
     }
-    IQR_HIP(hipEventRecord(r->ev[1], s));
+    IQPT_HIP(hipEventRecord(r->ev[1], s));
 
     uint32_t nrec = 0, npairs = 0;
     if (int st = build_lists(r, g, fp, false, r->draw_lists, r->ev + 2, nrec, npairs)) return st;
-    IQR_HIP(hipEventRecord(r->ev[4], s));
+    IQPT_HIP(hipEventRecord(r->ev[4], s));
     const lists& l = r->draw_lists;
-    IQR_HIP(iqr::launch_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
+    IQPT_HIP(iqr::launch_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
                               r->frame.as<uint32_t>(), nullptr, nullptr));
-    IQR_HIP(hipEventRecord(r->ev[5], s));
+    IQPT_HIP(hipEventRecord(r->ev[5], s));
     r->pending = true;
     r->have_frame = true;
     r->last_nrec = nrec;
@@ -248,7 +237,7 @@ int iqpt_raster_create(int device, uint32_t width, uint32_t height, uint32_t sam
     r->fp.ntx = (width + iqr::kTile - 1) / iqr::kTile;
     r->fp.nty = (height + iqr::kTile - 1) / iqr::kTile;
     auto fail_with = [&](hipError_t e, const char* what) {
-        const int st = hip_fail(e, what);
+        const int st = iqpt::hip_fail(e, what);
         iqpt_raster_destroy(r);
         return st;
     };
@@ -300,8 +289,8 @@ int iqpt_raster_set_camera(iqpt_raster* r, const iqpt_camera* cam) {
     std::memcpy(m, cam->view, 64);
     std::memcpy(m + 16, cam->projection, 64);
     // ordered behind the draws in flight; m is on the stack, so the copy is finished before returning
-    IQR_HIP(hipMemcpyAsync(r->camera.p, m, sizeof m, hipMemcpyHostToDevice, r->stream));
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    IQPT_HIP(hipMemcpyAsync(r->camera.p, m, sizeof m, hipMemcpyHostToDevice, r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     r->host_camera = *cam;
     r->have_camera = true;
     r->scene.transformed = false;
@@ -362,7 +351,7 @@ int iqpt_raster_upload_scene(iqpt_raster* r, const iqpt_scene* scene) {
     }
 
     if (int st = set_device(r)) return st;
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     geometry& g = r->scene;
     hipStream_t s = r->stream;
     if (int st = upload(g.draws, draws.data(), draws.size() * sizeof(iqr::draw_rec), s)) return st;
@@ -370,9 +359,9 @@ int iqpt_raster_upload_scene(iqpt_raster* r, const iqpt_scene* scene) {
     if (int st = upload(g.tend, tend.data(), tend.size() * 4, s)) return st;
     if (int st = upload(g.indices, indices.data(), indices.size() * 4, s)) return st;
     if (int st = upload(g.mesh_verts, verts.data(), verts.size() * 4, s)) return st;
-    IQR_HIP(g.clip.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
-    IQR_HIP(g.wn.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
-    IQR_HIP(hipStreamSynchronize(s));              // the host vectors go out of scope
+    IQPT_HIP(g.clip.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
+    IQPT_HIP(g.wn.reserve(std::max<size_t>((size_t)nverts * 16, 16)));
+    IQPT_HIP(hipStreamSynchronize(s));              // the host vectors go out of scope
     g.ndraws = (uint32_t)draws.size();
     g.nverts = (uint32_t)nverts;
     g.ntris = (uint32_t)ntris;
@@ -398,7 +387,7 @@ int iqpt_raster_draw_clip(iqpt_raster* r, const float* clip_xyzw, const float* n
     for (uint32_t k = 0; k < nindices; ++k)
         if (indices[k] >= nverts) return iqpt::fail(IQPT_ERR_INVALID_ARG, "index out of range");
     if (int st = set_device(r)) return st;
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     std::vector<float> c4((size_t)nverts * 4), n4((size_t)nverts * 4, 0.0f);
     if (nverts) std::memcpy(c4.data(), clip_xyzw, c4.size() * 4);
     for (uint32_t i = 0; i < nverts; ++i)
@@ -414,7 +403,7 @@ int iqpt_raster_draw_clip(iqpt_raster* r, const float* clip_xyzw, const float* n
     if (int st = upload(g.indices, indices, (size_t)nindices * 4, s)) return st;
     if (int st = upload(g.clip, c4.data(), c4.size() * 4, s)) return st;
     if (int st = upload(g.wn, n4.data(), n4.size() * 4, s)) return st;
-    IQR_HIP(hipStreamSynchronize(s));
+    IQPT_HIP(hipStreamSynchronize(s));
     g.ndraws = 1;
     g.nverts = nverts;
     g.ntris = ntris;
@@ -429,17 +418,17 @@ int iqpt_raster_read(iqpt_raster* r, uint8_t* bgra, float* depth_samples, uint32
     const size_t npix = (size_t)r->fp.width * r->fp.height, nsamp = npix * r->fp.samples;
     if (depth_samples || prim_samples) {
         // the tile kernel of the last draw again, over the same sorted lists, with the per-sample outputs on
-        IQR_HIP(r->depth_samples.reserve(nsamp * 4));
-        IQR_HIP(r->prim_samples.reserve(nsamp * 4));
+        IQPT_HIP(r->depth_samples.reserve(nsamp * 4));
+        IQPT_HIP(r->prim_samples.reserve(nsamp * 4));
         const lists& l = r->draw_lists;
-        IQR_HIP(iqr::launch_tiles(s, r->fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(),
+        IQPT_HIP(iqr::launch_tiles(s, r->fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(),
                                   l.ranges.as<uint32_t>(), r->frame.as<uint32_t>(), r->depth_samples.as<float>(),
                                   r->prim_samples.as<uint32_t>()));
-        if (depth_samples) IQR_HIP(hipMemcpyAsync(depth_samples, r->depth_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
-        if (prim_samples) IQR_HIP(hipMemcpyAsync(prim_samples, r->prim_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
+        if (depth_samples) IQPT_HIP(hipMemcpyAsync(depth_samples, r->depth_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
+        if (prim_samples) IQPT_HIP(hipMemcpyAsync(prim_samples, r->prim_samples.p, nsamp * 4, hipMemcpyDeviceToHost, s));
     }
-    if (bgra) IQR_HIP(hipMemcpyAsync(bgra, r->frame.p, npix * 4, hipMemcpyDeviceToHost, s));
-    IQR_HIP(hipStreamSynchronize(s));
+    if (bgra) IQPT_HIP(hipMemcpyAsync(bgra, r->frame.p, npix * 4, hipMemcpyDeviceToHost, s));
+    IQPT_HIP(hipStreamSynchronize(s));
     return IQPT_OK;
 }
 
@@ -448,15 +437,15 @@ int iqpt_raster_copy_frame_device(iqpt_raster* r, void* dst_device, size_t bytes
     if (!r->have_frame) return iqpt::fail(IQPT_ERR_NOT_READY, "copy before the first draw");
     if (bytes != (size_t)r->fp.width * r->fp.height * 4) return iqpt::fail(IQPT_ERR_INVALID_ARG, "bytes must be width*height*4");
     if (int st = set_device(r)) return st;
-    IQR_HIP(hipMemcpyAsync(dst_device, r->frame.p, bytes, hipMemcpyDeviceToDevice, r->stream));
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    IQPT_HIP(hipMemcpyAsync(dst_device, r->frame.p, bytes, hipMemcpyDeviceToDevice, r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     return IQPT_OK;
 }
 
 int iqpt_raster_sync(iqpt_raster* r) {
     if (!r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "rasterizer is NULL");
     if (int st = set_device(r)) return st;
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     return IQPT_OK;
 }
 
@@ -500,13 +489,13 @@ int iqpt_raster_gbuffer(iqpt_raster* r) {
     if (int st = collect_guide(r)) return st;
     hipStream_t s = r->stream;
     const size_t npix = (size_t)r->fp.width * r->fp.height;
-    IQR_HIP(r->guide_nz.reserve(npix * 16));
-    IQR_HIP(r->guide_id.reserve(npix * 4));
+    IQPT_HIP(r->guide_nz.reserve(npix * 16));
+    IQPT_HIP(r->guide_id.reserve(npix * 4));
     iqr::frame_params fp = r->fp;
     fp.samples = 1;                            // one sample per pixel, whatever the rasterizer's own count
-    IQR_HIP(hipEventRecord(r->guide_ev[0], s));
+    IQPT_HIP(hipEventRecord(r->guide_ev[0], s));
     if (!g.transformed) {
-        IQR_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
+        IQPT_HIP(iqr::launch_vertex(s, g.draws.as<iqr::draw_rec>(), g.ndraws, g.vend.as<uint32_t>(), g.nverts,
                                    g.mesh_verts.as<float>(), r->camera.as<float>(), r->camera.as<float>() + 16,
                                    g.clip.as<float>(), g.wn.as<float>()));
         g.transformed = true;
@@ -514,9 +503,9 @@ int iqpt_raster_gbuffer(iqpt_raster* r) {
     uint32_t nrec = 0, npairs = 0;
     lists& l = r->guide_lists;
     if (int st = build_lists(r, g, fp, true, l, nullptr, nrec, npairs)) return st;
-    IQR_HIP(iqr::launch_guide_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
+    IQPT_HIP(iqr::launch_guide_tiles(s, fp, l.recs.as<iqr::setup_rec>(), l.vals[1].as<uint32_t>(), l.ranges.as<uint32_t>(),
                                     r->guide_nz.p, r->guide_id.as<uint32_t>()));
-    IQR_HIP(hipEventRecord(r->guide_ev[1], s));
+    IQPT_HIP(hipEventRecord(r->guide_ev[1], s));
     r->guide_pending = true;
     r->guide_passes += 1;
     r->have_gbuffer = true;
@@ -528,9 +517,9 @@ int iqpt_raster_read_gbuffer(iqpt_raster* r, float* normal_z, uint32_t* id) {
     if (!r->have_gbuffer) return iqpt::fail(IQPT_ERR_NOT_READY, "read_gbuffer without a G-buffer of the current camera and scene");
     if (int st = set_device(r)) return st;
     const size_t npix = (size_t)r->fp.width * r->fp.height;
-    if (normal_z) IQR_HIP(hipMemcpyAsync(normal_z, r->guide_nz.p, npix * 16, hipMemcpyDeviceToHost, r->stream));
-    if (id) IQR_HIP(hipMemcpyAsync(id, r->guide_id.p, npix * 4, hipMemcpyDeviceToHost, r->stream));
-    IQR_HIP(hipStreamSynchronize(r->stream));
+    if (normal_z) IQPT_HIP(hipMemcpyAsync(normal_z, r->guide_nz.p, npix * 16, hipMemcpyDeviceToHost, r->stream));
+    if (id) IQPT_HIP(hipMemcpyAsync(id, r->guide_id.p, npix * 4, hipMemcpyDeviceToHost, r->stream));
+    IQPT_HIP(hipStreamSynchronize(r->stream));
     return IQPT_OK;
 }
 
@@ -538,7 +527,7 @@ int iqpt_raster_gbuffer_device(iqpt_raster* r, const void** normal_z, const void
     if (!r || !normal_z || !id) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     if (!r->have_gbuffer) return iqpt::fail(IQPT_ERR_NOT_READY, "gbuffer_device without a G-buffer of the current camera and scene");
     if (int st = set_device(r)) return st;
-    IQR_HIP(hipStreamSynchronize(r->stream));  // the caller reads them on a stream of its own
+    IQPT_HIP(hipStreamSynchronize(r->stream));  // the caller reads them on a stream of its own
     *normal_z = r->guide_nz.p;
     *id = r->guide_id.p;
     return IQPT_OK;

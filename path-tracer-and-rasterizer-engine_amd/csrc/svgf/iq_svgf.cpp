@@ -6,25 +6,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <string>
 #include <vector>
 
-#include "iqpt_internal.hpp"
-#include "raster/iq_raster.hpp"
+#include "post/iq_post.hpp"
 #include "svgf/iq_svgf.hpp"
 #include "svgf/iqpt_svgf.h"
+#include "temporal/iq_temporal.hpp"
 
 namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-    return iqpt::fail(IQPT_ERR_HIP, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
-}
-
-#define IQS_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);    \
-    } while (0)
 
 constexpr int kMaxLevels = IQPT_SVGF_MAX_LEVELS;
 // DESIGN.md §12.5 "Defaults": §11's three temporal values (not measured), §10.5's q and s_z, and the lowest mean
@@ -32,10 +21,7 @@ constexpr int kMaxLevels = IQPT_SVGF_MAX_LEVELS;
 constexpr iqpt_svgf_params kDefaults = {0.9f, 0.01f, 256u, 2u, 4u, 5u, 1024.0f, 8.0f, 0.01f};
 
 int check_params(const iqpt_svgf_params& p) {
-    if (!std::isfinite(p.normal_min)) return iqpt::fail(IQPT_ERR_INVALID_ARG, "normal_min must be finite");
-    if (!(p.plane_tolerance >= 0.0f)) return iqpt::fail(IQPT_ERR_INVALID_ARG, "plane_tolerance must be >= 0");
-    if (p.max_history < 1u || p.max_history > IQPT_TEMPORAL_MAX_HISTORY)
-        return iqpt::fail(IQPT_ERR_INVALID_ARG, "max_history must be 1..2^24");
+    if (int st = iqt::check_params({p.normal_min, p.plane_tolerance, p.max_history})) return st;
     if (p.min_history < 1u || p.min_history > IQPT_TEMPORAL_MAX_HISTORY)
         return iqpt::fail(IQPT_ERR_INVALID_ARG, "min_history must be 1..2^24");
     if (p.levels > IQPT_SVGF_MAX_LEVELS) return iqpt::fail(IQPT_ERR_INVALID_ARG, "levels must be 0..8");
@@ -51,10 +37,7 @@ int check_params(const iqpt_svgf_params& p) {
 
 }  // namespace
 
-struct iqpt_svgf {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint32_t width = 0, height = 0;
+struct iqpt_svgf : iqp::frame {
     iqpt_svgf_params params = kDefaults;
     iqpt_temporal* colour_t = nullptr;     // §11 unchanged
     iqpt_temporal* moments_t = nullptr;    // the same camera, planes and n, fed (L, L L, +0, +0)
@@ -68,44 +51,23 @@ struct iqpt_svgf {
     uint32_t* spatial = nullptr;           // one per block, device: the spatial-estimate counts of the last resolve
     const void* result = nullptr;          // c0 or one of colour[]
     bool have_view = false, have_result = false;
-    hipEvent_t ev_moments[2] = {};
-    hipEvent_t ev[kMaxLevels + 2] = {};    // before the variance kernel, after it, after every level
-    uint32_t pending_levels = 0;
-    bool pending = false;                  // the events of the last resolve have not been added up yet
-    double moments_ms = 0.0, variance_ms = 0.0, level_ms[kMaxLevels] = {};
-    uint64_t resolves = 0;
-    size_t npix() const { return (size_t)width * height; }
+    iqp::event_timer moments_tm;           // ev[0], ev[1] around the moments kernel
+    // ev[0], ev[1] around the variance kernel, ev[2 + i] after level i (or after the encoding, levels = 0)
+    iqp::event_timer chain_tm;
 };
+static_assert(kMaxLevels + 2 <= iqp::event_timer::kMaxEvents, "an event after every level");
 
 namespace {
 
-int set_device(iqpt_svgf* s) {
-    IQS_HIP(hipSetDevice(s->device));
-    return IQPT_OK;
-}
-
+// the chain's last event is the stream's last, so the moments kernel's pair needs no wait of its own
 int collect(iqpt_svgf* s) {
-    if (!s->pending) return IQPT_OK;
-    IQS_HIP(hipEventSynchronize(s->ev[1 + s->pending_levels]));
-    float ms = 0.0f;
-    IQS_HIP(hipEventElapsedTime(&ms, s->ev_moments[0], s->ev_moments[1]));
-    s->moments_ms += ms;
-    IQS_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    s->variance_ms += ms;
-    for (uint32_t k = 0; k < s->pending_levels; ++k) {
-        IQS_HIP(hipEventElapsedTime(&ms, s->ev[1 + k], s->ev[2 + k]));
-        s->level_ms[k] += ms;
-    }
-    s->resolves += 1;
-    s->pending = false;
-    return IQPT_OK;
+    if (int st = s->chain_tm.collect()) return st;
+    return s->moments_tm.collect(false);
 }
 
-int check_camera(const iqpt_svgf* s, const iqpt_camera* cam) {
-    if (cam->width != s->width || cam->height != s->height)
-        return iqpt::fail(IQPT_ERR_INVALID_ARG, "camera size differs from the frame's");
-    return IQPT_OK;
-}
+}  // namespace
+
+namespace {
 
 // the new view's planes are in s->normal_z / s->id already: both histories take them from there
 int begin(iqpt_svgf* s, const iqpt_camera* cam) {
@@ -117,16 +79,24 @@ int begin(iqpt_svgf* s, const iqpt_camera* cam) {
     return IQPT_OK;
 }
 
+int begin_planes(iqpt_svgf* s, const iqpt_camera* cam, const void* normal_z, const void* id, hipMemcpyKind kind) {
+    if (int st = iqp::check_camera(*s, cam)) return st;
+    if (int st = iqp::set_device(*s)) return st;
+    IQPT_HIP(hipStreamSynchronize(s->stream));      // levels in flight may still read the old planes
+    if (int st = iqp::copy_guides(*s, s->normal_z, s->id, normal_z, id, kind)) return st;
+    return begin(s, cam);
+}
+
 int resolve(iqpt_svgf* s, const void* colour_device, uint64_t n) {
     if (!s->have_view) return iqpt::fail(IQPT_ERR_NOT_READY, "resolve before the first begin_view");
     if (int st = collect(s)) return st;
     hipStream_t q = s->stream;
     const iqpt_svgf_params& p = s->params;
     // M on the object's stream, waited for: the moments history reads it on a stream of its own
-    IQS_HIP(hipEventRecord(s->ev_moments[0], q));
-    IQS_HIP(iqs::launch_moments(q, (uint32_t)s->npix(), colour_device, s->moments));
-    IQS_HIP(hipEventRecord(s->ev_moments[1], q));
-    IQS_HIP(hipStreamSynchronize(q));
+    IQPT_HIP(hipEventRecord(s->moments_tm.ev[0], q));
+    IQPT_HIP(iqs::launch_moments(q, (uint32_t)s->npix(), colour_device, s->moments));
+    IQPT_HIP(hipEventRecord(s->moments_tm.ev[1], q));
+    IQPT_HIP(hipStreamSynchronize(q));
     if (int st = iqpt_temporal_resolve_device(s->colour_t, colour_device, n)) return st;
     if (int st = iqpt_temporal_resolve_device(s->moments_t, s->moments, n)) return st;
     const void *o = nullptr, *mu = nullptr;
@@ -141,13 +111,13 @@ int resolve(iqpt_svgf* s, const void* colour_device, uint64_t n) {
     vp.height = s->height;
     vp.ne = std::fmax(nf, 1.0f);
     vp.min_weight = (float)p.min_history * vp.ne;
-    IQS_HIP(hipEventRecord(s->ev[0], q));
-    IQS_HIP(iqs::launch_variance(q, vp, o, mu, s->id, s->c0, s->spatial));
-    IQS_HIP(hipEventRecord(s->ev[1], q));
+    IQPT_HIP(hipEventRecord(s->chain_tm.ev[0], q));
+    IQPT_HIP(iqs::launch_variance(q, vp, o, mu, s->id, s->c0, s->spatial));
+    IQPT_HIP(hipEventRecord(s->chain_tm.ev[1], q));
     s->result = s->c0;
     if (p.levels == 0) {
-        IQS_HIP(iqs::launch_encode(q, s->width, s->height, s->c0, s->bgra));
-        IQS_HIP(hipEventRecord(s->ev[2], q));
+        IQPT_HIP(iqp::launch_encode(q, s->width, s->height, s->c0, s->bgra));
+        IQPT_HIP(hipEventRecord(s->chain_tm.ev[2], q));
     }
     const void* in = s->c0;
     for (uint32_t i = 0; i < p.levels; ++i) {
@@ -160,13 +130,13 @@ int resolve(iqpt_svgf* s, const void* colour_device, uint64_t n) {
         lp.sigma2 = p.colour_sigma * p.colour_sigma;
         lp.variance_floor = p.variance_floor;
         void* out = s->colour[i & 1u];
-        IQS_HIP(iqs::launch_level(q, lp, in, s->normal_z, s->id, out, i + 1 == p.levels ? s->bgra : nullptr));
-        IQS_HIP(hipEventRecord(s->ev[2 + i], q));
+        IQPT_HIP(iqs::launch_level(q, lp, in, s->normal_z, s->id, out, i + 1 == p.levels ? s->bgra : nullptr));
+        IQPT_HIP(hipEventRecord(s->chain_tm.ev[2 + i], q));
         in = out;
         s->result = out;
     }
-    s->pending_levels = p.levels ? p.levels : 1u;
-    s->pending = true;
+    s->moments_tm.recorded = 2;
+    s->chain_tm.recorded = 2 + (int)(p.levels ? p.levels : 1u);
     s->have_result = true;
     return IQPT_OK;
 }
@@ -182,69 +152,35 @@ int iqpt_svgf_default_params(iqpt_svgf_params* out) {
 }
 
 int iqpt_svgf_create(int device, uint32_t width, uint32_t height, iqpt_svgf** out) {
-    if (!out) return iqpt::fail(IQPT_ERR_INVALID_ARG, "out is NULL");
-    *out = nullptr;
-    if (width == 0 || height == 0 || width > IQPT_RASTER_MAX_DIM || height > IQPT_RASTER_MAX_DIM)
-        return iqpt::fail(IQPT_ERR_INVALID_ARG, "frame size must be 1..8192 in each dimension");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return iqpt::fail(IQPT_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= count) return iqpt::fail(IQPT_ERR_NO_DEVICE, "device index out of range");
-
-    iqpt_svgf* s = new iqpt_svgf();
-    s->device = device;
-    s->width = width;
-    s->height = height;
-    auto fail_with = [&](hipError_t e, const char* what) {
-        const int st = hip_fail(e, what);
-        iqpt_svgf_destroy(s);
-        return st;
-    };
-    auto fail_status = [&](int st) {
-        const std::string detail = iqpt_last_error();      // destroy must not lose it
-        iqpt_svgf_destroy(s);
-        return iqpt::fail(st, detail);
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device)) != hipSuccess) return fail_with(e, "hipSetDevice");
-    if ((e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)) != hipSuccess) return fail_with(e, "hipStreamCreate");
-    for (hipEvent_t& ev : s->ev_moments)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return fail_with(e, "hipEventCreate");
-    for (hipEvent_t& ev : s->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return fail_with(e, "hipEventCreate");
-    if (int st = iqpt_temporal_create(device, width, height, &s->colour_t)) return fail_status(st);
-    if (int st = iqpt_temporal_create(device, width, height, &s->moments_t)) return fail_status(st);
-    const size_t n = s->npix();
-    if ((e = hipMalloc(&s->normal_z, n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(normal_z)");
-    if ((e = hipMalloc((void**)&s->id, n * 4)) != hipSuccess) return fail_with(e, "hipMalloc(id)");
-    if ((e = hipMalloc(&s->input, n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(input)");
-    if ((e = hipMalloc(&s->moments, n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(moments)");
-    if ((e = hipMalloc(&s->c0, n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(c0)");
-    if ((e = hipMalloc(&s->colour[0], n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(colour)");
-    if ((e = hipMalloc(&s->colour[1], n * 16)) != hipSuccess) return fail_with(e, "hipMalloc(colour)");
-    if ((e = hipMalloc((void**)&s->bgra, n * 4)) != hipSuccess) return fail_with(e, "hipMalloc(bgra)");
-    if ((e = hipMalloc((void**)&s->spatial, iqs::num_blocks(width, height) * 4)) != hipSuccess) return fail_with(e, "hipMalloc(spatial)");
-    iqpt_temporal_params tp = {kDefaults.normal_min, kDefaults.plane_tolerance, kDefaults.max_history};
-    if (int st = iqpt_temporal_set_params(s->colour_t, &tp)) return fail_status(st);
-    if (int st = iqpt_temporal_set_params(s->moments_t, &tp)) return fail_status(st);
-    *out = s;
-    return IQPT_OK;
+    return iqp::frame_create(device, width, height, out, iqpt_svgf_destroy, [](iqpt_svgf* s) {
+        if (int st = s->moments_tm.create(2)) return st;
+        if (int st = s->chain_tm.create(kMaxLevels + 2)) return st;
+        if (int st = iqpt_temporal_create(s->device, s->width, s->height, &s->colour_t)) return st;
+        if (int st = iqpt_temporal_create(s->device, s->width, s->height, &s->moments_t)) return st;
+        const size_t n = s->npix();
+        if (int st = iqp::frame_alloc(*s, {{&s->normal_z, n * 16, "hipMalloc(normal_z)"},
+                                           {(void**)&s->id, n * 4, "hipMalloc(id)"},
+                                           {&s->input, n * 16, "hipMalloc(input)"},
+                                           {&s->moments, n * 16, "hipMalloc(moments)"},
+                                           {&s->c0, n * 16, "hipMalloc(c0)"},
+                                           {&s->colour[0], n * 16, "hipMalloc(colour)"},
+                                           {&s->colour[1], n * 16, "hipMalloc(colour)"},
+                                           {(void**)&s->bgra, n * 4, "hipMalloc(bgra)"},
+                                           {(void**)&s->spatial, iqp::num_blocks(s->width, s->height) * 4, "hipMalloc(spatial)"}}))
+            return st;
+        const iqpt_temporal_params tp = {kDefaults.normal_min, kDefaults.plane_tolerance, kDefaults.max_history};
+        if (int st = iqpt_temporal_set_params(s->colour_t, &tp)) return st;
+        return iqpt_temporal_set_params(s->moments_t, &tp);
+    });
 }
 
+// The object's own stream first: its variance kernel reads both histories' results. Nothing of theirs reads this
+// object's buffers by then (resolve waits for both), so they go after it.
 int iqpt_svgf_destroy(iqpt_svgf* s) {
     if (!s) return IQPT_OK;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    iqp::frame_close(*s, {&s->moments_tm, &s->chain_tm});
     (void)iqpt_temporal_destroy(s->colour_t);
     (void)iqpt_temporal_destroy(s->moments_t);
-    for (void* p : {s->normal_z, (void*)s->id, s->input, s->moments, s->c0, s->colour[0], s->colour[1], (void*)s->bgra,
-                    (void*)s->spatial})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t ev : s->ev_moments)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : s->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
     return IQPT_OK;
 }
@@ -262,36 +198,19 @@ int iqpt_svgf_set_params(iqpt_svgf* s, const iqpt_svgf_params* p) {
 
 int iqpt_svgf_begin_view(iqpt_svgf* s, const iqpt_camera* cam, const float* normal_z, const uint32_t* id) {
     if (!s || !cam || !normal_z || !id) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
-    if (int st = check_camera(s, cam)) return st;
-    if (int st = set_device(s)) return st;
-    IQS_HIP(hipStreamSynchronize(s->stream));      // levels in flight may still read the old planes
-    IQS_HIP(hipMemcpyAsync(s->normal_z, normal_z, s->npix() * 16, hipMemcpyHostToDevice, s->stream));
-    IQS_HIP(hipMemcpyAsync(s->id, id, s->npix() * 4, hipMemcpyHostToDevice, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));      // the caller's arrays may go away
-    return begin(s, cam);
+    return begin_planes(s, cam, normal_z, id, hipMemcpyHostToDevice);
 }
 
 int iqpt_svgf_begin_view_device(iqpt_svgf* s, const iqpt_camera* cam, const void* normal_z_device, const void* id_device) {
     if (!s || !cam || !normal_z_device || !id_device) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
-    if (int st = check_camera(s, cam)) return st;
-    if (int st = set_device(s)) return st;
-    IQS_HIP(hipStreamSynchronize(s->stream));
-    IQS_HIP(hipMemcpyAsync(s->normal_z, normal_z_device, s->npix() * 16, hipMemcpyDeviceToDevice, s->stream));
-    IQS_HIP(hipMemcpyAsync(s->id, id_device, s->npix() * 4, hipMemcpyDeviceToDevice, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));      // the caller's planes may change (the G-buffer of the next camera)
-    return begin(s, cam);
+    return begin_planes(s, cam, normal_z_device, id_device, hipMemcpyDeviceToDevice);
 }
 
 int iqpt_svgf_begin_view_raster(iqpt_svgf* s, iqpt_raster* r) {
     if (!s || !r) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
-    uint32_t rw = 0, rh = 0;
-    iqr::frame_size(r, &rw, &rh);
-    if (rw != s->width || rh != s->height) return iqpt::fail(IQPT_ERR_INVALID_ARG, "the rasterizer's frame size differs from the object's");
-    const iqpt_camera* cam = iqr::current_camera(r);
-    if (!cam) return iqpt::fail(IQPT_ERR_NOT_READY, "begin_view_raster before the rasterizer's set_camera");
-    if (int st = iqpt_raster_gbuffer(r)) return st;
+    const iqpt_camera* cam = nullptr;
     const void *nz = nullptr, *id = nullptr;
-    if (int st = iqpt_raster_gbuffer_device(r, &nz, &id)) return st;
+    if (int st = iqp::raster_view(*s, r, "the object's", &cam, &nz, &id)) return st;
     return iqpt_svgf_begin_view_device(s, cam, nz, id);
 }
 
@@ -307,15 +226,15 @@ int iqpt_svgf_clear(iqpt_svgf* s) {
 int iqpt_svgf_resolve(iqpt_svgf* s, const float* colour, uint64_t n) {
     if (!s || !colour) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     if (!s->have_view) return iqpt::fail(IQPT_ERR_NOT_READY, "resolve before the first begin_view");
-    if (int st = set_device(s)) return st;
-    IQS_HIP(hipMemcpyAsync(s->input, colour, s->npix() * 16, hipMemcpyHostToDevice, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));      // the caller's array may go away
+    if (int st = iqp::set_device(*s)) return st;
+    IQPT_HIP(hipMemcpyAsync(s->input, colour, s->npix() * 16, hipMemcpyHostToDevice, s->stream));
+    IQPT_HIP(hipStreamSynchronize(s->stream));      // the caller's array may go away
     return resolve(s, s->input, n);
 }
 
 int iqpt_svgf_resolve_device(iqpt_svgf* s, const void* colour_device, uint64_t n) {
     if (!s || !colour_device) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     return resolve(s, colour_device, n);
 }
 
@@ -325,7 +244,7 @@ int iqpt_svgf_resolve_ctx(iqpt_svgf* s, iqpt_ctx* ctx) {
     if (int st = iqpt_num_pixels(ctx, &npix)) return st;
     if (npix != s->npix()) return iqpt::fail(IQPT_ERR_INVALID_ARG, "the context does not own a whole frame of the object's size");
     if (!s->have_view) return iqpt::fail(IQPT_ERR_NOT_READY, "resolve before the first begin_view");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     if (int st = iqpt_copy_accum_device(ctx, s->input, s->npix() * 16)) return st;
     if (int st = iqpt_frame_count(ctx, &frames)) return st;
     return resolve(s, s->input, frames);
@@ -334,47 +253,39 @@ int iqpt_svgf_resolve_ctx(iqpt_svgf* s, iqpt_ctx* ctx) {
 int iqpt_svgf_read(iqpt_svgf* s, float* lin_rgba, uint8_t* bgra) {
     if (!s) return iqpt::fail(IQPT_ERR_INVALID_ARG, "svgf object is NULL");
     if (!s->have_result) return iqpt::fail(IQPT_ERR_NOT_READY, "read before a resolve of the current view");
-    if (int st = set_device(s)) return st;
-    if (lin_rgba) IQS_HIP(hipMemcpyAsync(lin_rgba, s->result, s->npix() * 16, hipMemcpyDeviceToHost, s->stream));
-    if (bgra) IQS_HIP(hipMemcpyAsync(bgra, s->bgra, s->npix() * 4, hipMemcpyDeviceToHost, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));
-    return IQPT_OK;
+    return iqp::read_planes(*s, lin_rgba, s->result, bgra, s->bgra);
 }
 
 int iqpt_svgf_read_stages(iqpt_svgf* s, float* temporal_rgba, float* variance_rgba) {
     if (!s) return iqpt::fail(IQPT_ERR_INVALID_ARG, "svgf object is NULL");
     if (!s->have_result) return iqpt::fail(IQPT_ERR_NOT_READY, "read before a resolve of the current view");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     if (temporal_rgba)
         if (int st = iqpt_temporal_read(s->colour_t, temporal_rgba, nullptr)) return st;
-    if (variance_rgba) IQS_HIP(hipMemcpyAsync(variance_rgba, s->c0, s->npix() * 16, hipMemcpyDeviceToHost, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));
+    if (variance_rgba) IQPT_HIP(hipMemcpyAsync(variance_rgba, s->c0, s->npix() * 16, hipMemcpyDeviceToHost, s->stream));
+    IQPT_HIP(hipStreamSynchronize(s->stream));
     return IQPT_OK;
 }
 
 int iqpt_svgf_copy_frame_device(iqpt_svgf* s, void* dst_device, size_t bytes) {
     if (!s || !dst_device) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     if (!s->have_result) return iqpt::fail(IQPT_ERR_NOT_READY, "copy before a resolve of the current view");
-    if (bytes != s->npix() * 4) return iqpt::fail(IQPT_ERR_INVALID_ARG, "bytes must be width*height*4");
-    if (int st = set_device(s)) return st;
-    IQS_HIP(hipMemcpyAsync(dst_device, s->bgra, bytes, hipMemcpyDeviceToDevice, s->stream));
-    IQS_HIP(hipStreamSynchronize(s->stream));
-    return IQPT_OK;
+    return iqp::copy_bgra(*s, s->bgra, dst_device, bytes);
 }
 
 int iqpt_svgf_sync(iqpt_svgf* s) {
     if (!s) return iqpt::fail(IQPT_ERR_INVALID_ARG, "svgf object is NULL");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     if (int st = iqpt_temporal_sync(s->colour_t)) return st;
     if (int st = iqpt_temporal_sync(s->moments_t)) return st;
-    IQS_HIP(hipStreamSynchronize(s->stream));
+    IQPT_HIP(hipStreamSynchronize(s->stream));
     return IQPT_OK;
 }
 
 int iqpt_svgf_time(iqpt_svgf* s, double* moments_ms, double* variance_ms, double* level_ms, uint64_t* resolves,
                    double* view_ms, double* history_resolve_ms) {
     if (!s || !moments_ms || !variance_ms || !resolves) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     if (int st = collect(s)) return st;
     iqpt_temporal* both[2] = {s->colour_t, s->moments_t};
     for (int k = 0; k < 2; ++k) {
@@ -384,28 +295,26 @@ int iqpt_svgf_time(iqpt_svgf* s, double* moments_ms, double* variance_ms, double
         if (view_ms) view_ms[k] = vms;
         if (history_resolve_ms) history_resolve_ms[k] = rms;
     }
-    *moments_ms = s->moments_ms;
-    *variance_ms = s->variance_ms;
-    *resolves = s->resolves;
-    for (int k = 0; k < kMaxLevels; ++k) {
-        if (level_ms) level_ms[k] = s->level_ms[k];
-        s->level_ms[k] = 0.0;
-    }
-    s->moments_ms = s->variance_ms = 0.0;
-    s->resolves = 0;
+    *moments_ms = s->moments_tm.ms[0];
+    *variance_ms = s->chain_tm.ms[0];
+    *resolves = s->chain_tm.runs;
+    for (int k = 0; k < kMaxLevels; ++k)
+        if (level_ms) level_ms[k] = s->chain_tm.ms[1 + k];
+    s->moments_tm.reset();
+    s->chain_tm.reset();
     return IQPT_OK;
 }
 
 int iqpt_svgf_stats(iqpt_svgf* s, uint64_t* guided, uint64_t* valid, uint64_t* spatial) {
     if (!s || !guided || !valid || !spatial) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     if (!s->have_view) return iqpt::fail(IQPT_ERR_NOT_READY, "stats before the first begin_view");
-    if (int st = set_device(s)) return st;
+    if (int st = iqp::set_device(*s)) return st;
     if (int st = iqpt_temporal_stats(s->colour_t, guided, valid)) return st;
     uint64_t sum = 0;
     if (s->have_result) {
-        std::vector<uint32_t> host(iqs::num_blocks(s->width, s->height));
-        IQS_HIP(hipMemcpyAsync(host.data(), s->spatial, host.size() * 4, hipMemcpyDeviceToHost, s->stream));
-        IQS_HIP(hipStreamSynchronize(s->stream));
+        std::vector<uint32_t> host(iqp::num_blocks(s->width, s->height));
+        IQPT_HIP(hipMemcpyAsync(host.data(), s->spatial, host.size() * 4, hipMemcpyDeviceToHost, s->stream));
+        IQPT_HIP(hipStreamSynchronize(s->stream));
         for (uint32_t c : host) sum += c;
     }
     *spatial = sum;

@@ -4,13 +4,14 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include <cstddef>
 #include <cstdint>
+
+#include "post/iq_post_device.hpp"
 
 namespace iqs {
 
-constexpr int kBlockX = 32;   // the denoiser's block: lanes run along x
-constexpr int kBlockY = 8;
+using iqp::kBlockX;
+using iqp::kBlockY;
 constexpr int kHalo = 3;      // the spatial estimate's window is 7 x 7
 constexpr int kTileW = kBlockX + 2 * kHalo, kTileH = kBlockY + 2 * kHalo;   // 38 x 14 entries staged in LDS
 
@@ -33,15 +34,11 @@ struct level_params {
 // M = (L, L L, +0, +0) of npix colours.
 hipError_t launch_moments(hipStream_t s, uint32_t npix, const void* colour, void* moments);
 // c0 = (o.xyz, v) of the two histories' results; block_spatial[block] = the block's pixels that took the spatial
-// estimate, one entry per 32x8 block of the grid, row-major (num_blocks entries).
+// estimate, one entry per 32x8 block of the grid, row-major (iqp::num_blocks entries).
 hipError_t launch_variance(hipStream_t s, const variance_params& p, const void* o, const void* mu, const uint32_t* id,
                            void* c0, uint32_t* block_spatial);
-inline size_t num_blocks(uint32_t width, uint32_t height) {
-    return (size_t)((width + kBlockX - 1) / kBlockX) * ((height + kBlockY - 1) / kBlockY);
-}
-// One level; bgra != NULL: the last one, which also encodes.
+// One level; bgra != NULL: the last one, which also encodes. levels = 0 is iqp::launch_encode of c0.
 hipError_t launch_level(hipStream_t s, const level_params& p, const void* in, const void* normal_z, const uint32_t* id,
                         void* out, uint32_t* bgra);
-hipError_t launch_encode(hipStream_t s, uint32_t width, uint32_t height, const void* in, uint32_t* bgra);
 
 }  // namespace iqs

@@ -1,32 +1,18 @@
 // iq_svgf_kernels.hip — the variance-guided filter's kernels for gfx950 (wave64), lane = pixel: the luminance
 // moments of a colour plane, the per-pixel variance estimate (temporal from the moments history, spatial from a
-// 7x7 window staged in LDS), one variance-guided à-trous level per launch and the BGRA8 encoding. DESIGN.md §12 is
-// the definition these restate; every float operation below is written in that section's order and compiled with
-// -ffp-contract=off and correctly rounded division and square root.
+// 7x7 window staged in LDS) and one variance-guided à-trous level per launch, over the tap and the BGRA8 encoding
+// of post/iq_post_device.hpp. DESIGN.md §12 is the definition these restate; every float operation below is
+// written in that section's order and compiled with -ffp-contract=off and correctly rounded division and square
+// root.
 #include <hip/hip_runtime.h>
 
 #include "svgf/iq_svgf.hpp"
 
 namespace iqs {
 
+using namespace iqp;
+
 namespace {
-
-constexpr uint32_t kNoPrim = 0xffffffffu;
-
-__device__ inline bool finite1(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ inline bool finite3(const float4& c) { return finite1(c.x) && finite1(c.y) && finite1(c.z); }
-
-// uint8_t conversion of the path tracer's frame: NaN -> 0, saturate to [0, 255], truncate toward zero
-__device__ inline uint32_t to_u8(float f) {
-    if (!(f > 0.0f)) return 0u;
-    if (f >= 255.0f) return 255u;
-    return (uint32_t)f;
-}
-
-__device__ inline uint32_t encode(const float4& c) {
-    return to_u8(255.0f * sqrtf(c.z)) | to_u8(255.0f * sqrtf(c.y)) << 8 | to_u8(255.0f * sqrtf(c.x)) << 16 | 0xff000000u;
-}
 
 __device__ inline float luminance(const float4& c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
@@ -142,6 +128,7 @@ __global__ void __launch_bounds__(kBlockX* kBlockY) iqs_level_kernel(level_param
     const uint32_t idp = id[pix];
     float4 res = cp;
     if (idp != kNoPrim && finite3(cp)) {
+        const atrous_planes a = {p.width, p.height, in, normal_z, id};
         const float g[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
         float vsum = 0.0f, gsum = 0.0f;
 #pragma unroll
@@ -154,12 +141,9 @@ __global__ void __launch_bounds__(kBlockX* kBlockY) iqs_level_kernel(level_param
                     gsum = gsum + gw;
                     continue;
                 }
-                const int qx = px + dx, qy = py + dy;
-                if (qx < 0 || qy < 0 || qx >= (int)p.width || qy >= (int)p.height) continue;
-                const size_t q = (size_t)qy * p.width + (size_t)qx;
-                if (id[q] != idp) continue;
-                const float4 cq = in[q];
-                if (!finite3(cq)) continue;
+                size_t q;
+                float4 cq;
+                if (!tap_colour(a, px + dx, py + dy, idp, q, cq)) continue;
                 vsum = vsum + gw * cq.w;
                 gsum = gsum + gw;
             }
@@ -183,20 +167,11 @@ __global__ void __launch_bounds__(kBlockX* kBlockY) iqs_level_kernel(level_param
                     vnum = vnum + (hw * hw) * cp.w;
                     continue;
                 }
-                const int qx = px + dx * p.step, qy = py + dy * p.step;
-                if (qx < 0 || qy < 0 || qx >= (int)p.width || qy >= (int)p.height) continue;
-                const size_t q = (size_t)qy * p.width + (size_t)qx;
-                if (id[q] != idp) continue;
-                const float4 cq = in[q];
-                if (!finite3(cq)) continue;
-                const float4 nq = normal_z[q];
-                float d = fmaxf(np.x * nq.x + np.y * nq.y + np.z * nq.z, 0.0f);
-                for (uint32_t k = 0; k < p.squarings; ++k) d = d * d;
-                const float t = (np.w - nq.w) * p.depth_sharpness;
-                const float ex = cp.x - cq.x, ey = cp.y - cq.y, ez = cp.z - cq.z;
-                const float d2 = ex * ex + ey * ey + ez * ez;
-                const float w = (hw * d) / ((1.0f + t * t) * (1.0f + d2 * r));
-                if (!(w > 0.0f)) continue;      // a NaN weight fails too
+                size_t q;
+                float4 cq;
+                float w;
+                if (!tap_colour(a, px + dx * p.step, py + dy * p.step, idp, q, cq)) continue;
+                if (!tap_weight(a, q, cq, cp, np, hw, p.squarings, p.depth_sharpness, r, w)) continue;
                 nx = nx + w * cq.x;
                 ny = ny + w * cq.y;
                 nz = nz + w * cq.z;
@@ -208,19 +183,6 @@ __global__ void __launch_bounds__(kBlockX* kBlockY) iqs_level_kernel(level_param
     }
     out[pix] = res;
     if (kEncode) bgra[pix] = encode(res);
-}
-
-__global__ void __launch_bounds__(kBlockX* kBlockY) iqs_encode_kernel(uint32_t width, uint32_t height,
-                                                                      const float4* __restrict__ in,
-                                                                      uint32_t* __restrict__ bgra) {
-    const uint32_t px = blockIdx.x * kBlockX + threadIdx.x, py = blockIdx.y * kBlockY + threadIdx.y;
-    if (px >= width || py >= height) return;
-    const size_t pix = (size_t)py * width + px;
-    bgra[pix] = encode(in[pix]);
-}
-
-inline dim3 grid(uint32_t width, uint32_t height) {
-    return dim3((width + kBlockX - 1) / kBlockX, (height + kBlockY - 1) / kBlockY);
 }
 
 }  // namespace
@@ -247,11 +209,6 @@ hipError_t launch_level(hipStream_t s, const level_params& p, const void* in, co
     else
         iqs_level_kernel<false><<<g, b, 0, s>>>(p, static_cast<const float4*>(in), static_cast<const float4*>(normal_z), id,
                                                 static_cast<float4*>(out), nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_encode(hipStream_t s, uint32_t width, uint32_t height, const void* in, uint32_t* bgra) {
-    iqs_encode_kernel<<<grid(width, height), dim3(kBlockX, kBlockY), 0, s>>>(width, height, static_cast<const float4*>(in), bgra);
     return hipGetLastError();
 }
 

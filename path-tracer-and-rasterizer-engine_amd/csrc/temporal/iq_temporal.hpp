@@ -6,10 +6,13 @@
 
 #include <cstdint>
 
+struct iqpt_temporal_params;
+
 namespace iqt {
 
-constexpr int kBlockX = 32;   // the denoiser's block: lanes run along x, every plane access of a wave two row segments
-constexpr int kBlockY = 8;
+// IQPT_OK, or the status of the first field out of range with its message as the last error (iq_temporal.cpp);
+// the variance-guided filter checks the same three fields of its own parameters with it.
+int check_params(const iqpt_temporal_params& p);
 
 // Kernel arguments of one begin_view: wave-uniform, so the 64 matrix words are read through the scalar cache.
 struct view_params {

@@ -5,29 +5,14 @@
 // division and square root.
 #include <hip/hip_runtime.h>
 
+#include "post/iq_post_device.hpp"
 #include "temporal/iq_temporal.hpp"
 
 namespace iqt {
 
+using namespace iqp;
+
 namespace {
-
-constexpr uint32_t kNoPrim = 0xffffffffu;
-
-__device__ inline bool finite3(const float4& c) {
-    return (__float_as_uint(c.x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(c.y) & 0x7f800000u) != 0x7f800000u &&
-           (__float_as_uint(c.z) & 0x7f800000u) != 0x7f800000u;
-}
-
-// uint8_t conversion of the path tracer's frame: NaN -> 0, saturate to [0, 255], truncate toward zero
-__device__ inline uint32_t to_u8(float f) {
-    if (!(f > 0.0f)) return 0u;
-    if (f >= 255.0f) return 255u;
-    return (uint32_t)f;
-}
-
-__device__ inline uint32_t encode(const float4& c) {
-    return to_u8(255.0f * sqrtf(c.z)) | to_u8(255.0f * sqrtf(c.y)) << 8 | to_u8(255.0f * sqrtf(c.x)) << 16 | 0xff000000u;
-}
 
 // (x, y, z, 1) times a row-major 4x4 as a row vector: each component a left-to-right sum over the column
 // (tests/raster_ref.py dot4; the product with w = 1 is exact, so the last term is the matrix word itself)
@@ -133,10 +118,6 @@ __global__ void __launch_bounds__(256) iqt_stats_kernel(uint32_t npix, const uin
         if (g) atomicAdd(&counts[0], (unsigned long long)__popcll(g));
         if (v) atomicAdd(&counts[1], (unsigned long long)__popcll(v));
     }
-}
-
-inline dim3 grid(uint32_t width, uint32_t height) {
-    return dim3((width + kBlockX - 1) / kBlockX, (height + kBlockY - 1) / kBlockY);
 }
 
 }  // namespace

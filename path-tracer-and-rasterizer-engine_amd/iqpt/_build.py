@@ -54,7 +54,9 @@ LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tra
                # temporal reprojection, likewise
                "temporal/iq_temporal_kernels.hip", "temporal/iq_temporal.cpp",
                # variance-guided filtering, likewise
-               "svgf/iq_svgf_kernels.hip", "svgf/iq_svgf.cpp"]
+               "svgf/iq_svgf_kernels.hip", "svgf/iq_svgf.cpp",
+               # what those three share, likewise
+               "post/iq_post_kernels.hip", "post/iq_post.cpp"]
 
 
 def _run(cmd: list[str], cwd: Path | None = None, stderr_to: Path | None = None) -> None:
@@ -89,25 +91,13 @@ def _headers() -> list[Path]:
     return sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 
 
-def _raster_headers() -> list[Path]:
-    return sorted((CSRC / "raster").glob("*.hpp")) + sorted((INCLUDE / "raster").glob("*.h"))
-
-
-def _denoise_headers() -> list[Path]:
-    return sorted((CSRC / "denoise").glob("*.hpp")) + sorted((INCLUDE / "denoise").glob("*.h"))
-
-
-def _temporal_headers() -> list[Path]:
-    return sorted((CSRC / "temporal").glob("*.hpp")) + sorted((INCLUDE / "temporal").glob("*.h"))
-
-
-def _svgf_headers() -> list[Path]:
-    return sorted((CSRC / "svgf").glob("*.hpp")) + sorted((INCLUDE / "svgf").glob("*.h"))
+SUBDIRS = ("raster", "denoise", "temporal", "svgf", "post")
 
 
 def _deps() -> list[Path]:
     """Every header a library object or a tool may include."""
-    return _headers() + _raster_headers() + _denoise_headers() + _temporal_headers() + _svgf_headers()
+    return _headers() + [h for d in SUBDIRS
+                         for h in sorted((CSRC / d).glob("*.hpp")) + sorted((INCLUDE / d).glob("*.h"))]
 
 
 def kernel_source_sha16() -> str:

@@ -1,11 +1,11 @@
 """The HIP denoiser and the rasterizer's G-buffer against their numpy reference (tests/denoise_ref.py, DESIGN.md
 §9.6 and §10): every float4 is compared as uint32, every BGRA byte for equality.
 
-Which case reaches which kernel instantiation (csrc/denoise/iq_denoise_kernels.hip ships three, all with direct
-global loads; there is no LDS variant):
+Which case reaches which kernel instantiation (csrc/denoise/iq_denoise_kernels.hip ships the two level kernels,
+csrc/post/iq_post_kernels.hip the encoding, all with direct global loads; there is no LDS variant):
   iqd_level_kernel<true>   (the last level, writes the BGRA frame too): every test_synthetic case, L = 1..5
   iqd_level_kernel<false>  (the levels before the last):                every test_synthetic case with L >= 2
-  iqd_encode_kernel        (L = 0, encoding only):                      test_zero_levels
+  iqp_encode_kernel        (L = 0, encoding only):                      test_zero_levels
 and csrc/raster/iq_raster_kernels.hip two for the G-buffer, reached by every test_gbuffer_* case:
   iqr_setup_kernel<true>, iqr_guide_tile_kernel."""
 import itertools

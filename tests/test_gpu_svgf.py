@@ -2,7 +2,8 @@
 compared as uint32, every BGRA byte for equality, every count for equality.
 
 csrc/svgf/iq_svgf_kernels.hip ships iqs_moments_kernel and iqs_variance_kernel (every resolve),
-iqs_level_kernel<false> and <true> (levels >= 2 and >= 1) and iqs_encode_kernel (levels == 0); all are reached by
+iqs_level_kernel<false> and <true> (levels >= 2 and >= 1), and levels == 0 runs iqp_encode_kernel of
+csrc/post/iq_post_kernels.hip; all are reached by
 every test_synthetic case, and both branches of the variance kernel by both values of min_history together."""
 import contextlib
 

@@ -11,6 +11,9 @@
 //     view's own frame and its temporal frame, which keeps the earlier views' samples, are written)
 //   iqpt_cli --preset cornell_lit --spp 1 --svgf --views 8 --step-x 0.05 --out last.ppm --out-svgf filtered.ppm
 //     (the same sequence through variance-guided filtering; may be combined with --temporal)
+//   iqpt_cli --preset cornell_lit --width 1920 --height 1080 --spp 4 --upscale 2 --out lo.ppm --out-upscaled full.ppm
+//     (guided upsampling, DESIGN.md §14: the path tracer runs at width/F x height/F, --out is that frame and
+//     --out-upscaled the full-size one; alone, not with --denoise, --temporal or --svgf)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,11 +23,13 @@
 
 #include "path_tracer.hpp"
 #include "raster/rasterizer.hpp"
+#include "upscale/upscaler.hpp"
 
 int main(int argc, char** argv) {
-    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised, out_temporal, out_svgf;
+    std::string preset = "cornell", out = "iqpt.ppm", engine = "pt", out_denoised, out_temporal, out_svgf, out_upscaled;
     int width = 640, height = 360, spp = 16, launches = 1, max_depth = 8, device = 0, samples = 4, denoise_levels = -1;
-    int views = -1;
+    int views = -1, upscale = 0;
+    bool have_upscale = false;
     float step_x = 0.0f;
     bool denoise = false, temporal = false, svgf = false, have_step = false;
     for (int i = 1; i < argc; i += 2) {
@@ -41,6 +46,11 @@ int main(int argc, char** argv) {
         else if (k == "--denoise-levels") denoise_levels = std::atoi(v);
         else if (k == "--out-temporal") out_temporal = v;
         else if (k == "--out-svgf") out_svgf = v;
+        else if (k == "--out-upscaled") out_upscaled = v;
+        else if (k == "--upscale") {
+            upscale = std::atoi(v);
+            have_upscale = true;
+        }
         else if (k == "--views") views = std::atoi(v);
         else if (k == "--step-x") {
             step_x = (float)std::atof(v);
@@ -92,10 +102,70 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--views and --step-x need --temporal or --svgf\n");
         return 2;
     }
+    if (have_upscale && (engine != "pt" || denoise || temporal || svgf || out_upscaled.empty())) {
+        std::fprintf(stderr, "--upscale goes with the path tracer alone and needs --out-upscaled PATH\n");
+        return 2;
+    }
+    if (!have_upscale && !out_upscaled.empty()) {
+        std::fprintf(stderr, "--out-upscaled needs --upscale\n");
+        return 2;
+    }
+    if (have_upscale && (upscale < (int)IQPT_UPSCALE_MIN_FACTOR || upscale > (int)IQPT_UPSCALE_MAX_FACTOR || width <= 0 ||
+                         height <= 0 || width % upscale != 0 || height % upscale != 0)) {
+        std::fprintf(stderr, "--upscale must be 2, 3 or 4 and divide --width and --height\n");
+        return 2;
+    }
     try {
         iqpt::camera cam((uint16_t)width, (uint16_t)height);
         iqpt::scene scn;
         scn.add_preset(preset);
+        if (have_upscale) {
+            // the contexts themselves: the path tracer and one rasterizer at the lo size, another rasterizer at the
+            // full size, all under one camera (its matrices do not depend on the frame size)
+            const uint32_t W = (uint32_t)width, H = (uint32_t)height, w = W / (uint32_t)upscale, h = H / (uint32_t)upscale;
+            iqpt::camera cam_lo((uint16_t)w, (uint16_t)h);
+            struct handles {                     // destroyed on every way out, after the upscaler declared below
+                iqpt_ctx* ctx = nullptr;
+                iqpt_raster *r_lo = nullptr, *r_hi = nullptr;
+                ~handles() {
+                    iqpt_raster_destroy(r_hi);
+                    iqpt_raster_destroy(r_lo);
+                    iqpt_destroy(ctx);
+                }
+            } own;
+            IQPT_THROW_FAILED(iqpt_create(device, w, h, nullptr, IQPT_DEFAULT_SEED, max_depth, &own.ctx));
+            IQPT_THROW_FAILED(iqpt_raster_create(device, w, h, 1, &own.r_lo));
+            IQPT_THROW_FAILED(iqpt_raster_create(device, W, H, 1, &own.r_hi));
+            iqpt_ctx* const ctx = own.ctx;
+            iqpt_raster *const r_lo = own.r_lo, *const r_hi = own.r_hi;
+            {
+                iqpt::upscaler up(W, H, (uint32_t)upscale, device);
+                const iqpt_packet_desc pk = scn.build_packet();
+                IQPT_THROW_FAILED(iqpt_set_camera(ctx, &cam_lo.raw()));
+                IQPT_THROW_FAILED(iqpt_upload_packet(ctx, &pk));
+                IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_lo, scn.handle()));
+                IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_hi, scn.handle()));
+                IQPT_THROW_FAILED(iqpt_raster_set_camera(r_lo, &cam_lo.raw()));
+                IQPT_THROW_FAILED(iqpt_raster_set_camera(r_hi, &cam.raw()));
+                for (int l = 0; l < launches; ++l) IQPT_THROW_FAILED(iqpt_render(ctx, (uint32_t)spp));
+                up.frame(ctx, r_lo, r_hi);
+                up.write_ppm(out_upscaled);
+                std::vector<uint8_t> bgra((size_t)w * h * 4);
+                IQPT_THROW_FAILED(iqpt_read(ctx, nullptr, bgra.data()));
+                IQPT_THROW_FAILED(iqpt_write_ppm(out.c_str(), w, h, bgra.data()));
+                const iqpt::upscaler::counts n = up.stats();
+                uint64_t frames = 0, runs = 0;
+                double ms = 0.0;
+                IQPT_THROW_FAILED(iqpt_frame_count(ctx, &frames));
+                IQPT_THROW_FAILED(iqpt_upscale_time(up.context(), &ms, &runs));
+                std::printf("{\"preset\": \"%s\", \"upscale\": %d, \"lo_width\": %u, \"lo_height\": %u, \"frames\": %llu, "
+                            "\"out\": \"%s\", \"out_upscaled\": \"%s\", \"guided\": %llu, \"widened\": %llu, "
+                            "\"unguided\": %llu, \"upscale_ms\": %.4f}\n",
+                            preset.c_str(), upscale, w, h, (unsigned long long)frames, out.c_str(), out_upscaled.c_str(),
+                            (unsigned long long)n.guided, (unsigned long long)n.widened, (unsigned long long)n.unguided, ms);
+            }
+            return 0;
+        }
         if (temporal || svgf) {
             // the contexts themselves (the facade's camera never moves): every view sets the moved camera on the
             // path tracer and the rasterizer, resets the accumulation, begins a temporal view (an svgf view, or both)

@@ -11,3 +11,4 @@ from .render import PathTracer, comm_unique_id, kernel_name, pixel_set, write_pp
 from .scene import CONFIGS, Config, Scene, config_scene, make_camera, packet_stats  # noqa: F401
 from .svgf import Svgf  # noqa: F401
 from .temporal import Temporal  # noqa: F401
+from .upscale import Upscaler  # noqa: F401

@@ -36,6 +36,7 @@ RASTER_FACADE_TEST_PATH = PKG_DIR / "test_raster_facade"
 DENOISE_FACADE_TEST_PATH = PKG_DIR / "test_denoise_facade"
 TEMPORAL_FACADE_TEST_PATH = PKG_DIR / "test_temporal_facade"
 SVGF_FACADE_TEST_PATH = PKG_DIR / "test_svgf_facade"
+UPSCALE_FACADE_TEST_PATH = PKG_DIR / "test_upscale_facade"
 
 ARCH = os.environ.get("IQPT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
@@ -56,7 +57,9 @@ LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tra
                # variance-guided filtering, likewise
                "svgf/iq_svgf_kernels.hip", "svgf/iq_svgf.cpp",
                # what those three share, likewise
-               "post/iq_post_kernels.hip", "post/iq_post.cpp"]
+               "post/iq_post_kernels.hip", "post/iq_post.cpp",
+               # guided upsampling, likewise
+               "upscale/iq_upscale_kernels.hip", "upscale/iq_upscale.cpp"]
 
 
 def _run(cmd: list[str], cwd: Path | None = None, stderr_to: Path | None = None) -> None:
@@ -91,7 +94,7 @@ def _headers() -> list[Path]:
     return sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 
 
-SUBDIRS = ("raster", "denoise", "temporal", "svgf", "post")
+SUBDIRS = ("raster", "denoise", "temporal", "svgf", "post", "upscale")
 
 
 def _deps() -> list[Path]:
@@ -144,8 +147,8 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
 
 
 def build_tools(force: bool = False) -> list[Path]:
-    """C++ programs over the facades: the headless CLI, the path_tracer facade test, the two-engine renderer test
-    and the tests of the renderer's denoise, temporal and svgf blocks."""
+    """C++ programs over the facades: the headless CLI, the path_tracer facade test, the two-engine renderer test,
+    the tests of the renderer's denoise, temporal and svgf blocks and the test of iqpt::upscaler."""
     lib = build_lib(force)
     out = []
     for src, dst in ((CSRC / "tools" / "iqpt_cli.cpp", CLI_PATH),
@@ -153,7 +156,8 @@ def build_tools(force: bool = False) -> list[Path]:
                      (CSRC / "tools" / "test_raster_facade.cpp", RASTER_FACADE_TEST_PATH),
                      (CSRC / "tools" / "test_denoise_facade.cpp", DENOISE_FACADE_TEST_PATH),
                      (CSRC / "tools" / "test_temporal_facade.cpp", TEMPORAL_FACADE_TEST_PATH),
-                     (CSRC / "tools" / "test_svgf_facade.cpp", SVGF_FACADE_TEST_PATH)):
+                     (CSRC / "tools" / "test_svgf_facade.cpp", SVGF_FACADE_TEST_PATH),
+                     (CSRC / "tools" / "test_upscale_facade.cpp", UPSCALE_FACADE_TEST_PATH)):
         if not src.exists():
             continue
         if force or not _newer(dst, [src, lib] + _deps()):

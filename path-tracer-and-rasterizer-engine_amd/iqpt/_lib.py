@@ -258,6 +258,33 @@ SVGF_SIGNATURES = [
     ("iqpt_svgf_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 ]
 
+
+class UpscaleParams(C.Structure):
+    """iqpt_upscale_params (include/upscale/iqpt_upscale.h)."""
+    _fields_ = [("normal_squarings", C.c_uint32), ("depth_sharpness", C.c_float)]
+
+
+_UP = C.POINTER(C.c_uint32)
+_U64P = C.POINTER(C.c_uint64)
+# the same for include/upscale/iqpt_upscale.h (guided upsampling's additions)
+UPSCALE_SIGNATURES = [
+    ("iqpt_upscale_default_params", C.c_int, [C.POINTER(UpscaleParams)]),
+    ("iqpt_upscale_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_upscale_destroy", C.c_int, [_P]),
+    ("iqpt_upscale_set_params", C.c_int, [_P, C.POINTER(UpscaleParams)]),
+    ("iqpt_upscale_set_guides", C.c_int, [_P, _FP, _UP, _FP, _UP]),
+    ("iqpt_upscale_set_guides_device", C.c_int, [_P, _P, _P, _P, _P]),
+    ("iqpt_upscale_run", C.c_int, [_P, _FP]),
+    ("iqpt_upscale_run_device", C.c_int, [_P, _P]),
+    ("iqpt_upscale_frame", C.c_int, [_P, _P, _P, _P]),
+    ("iqpt_upscale_read", C.c_int, [_P, _FP, C.POINTER(C.c_uint8)]),
+    ("iqpt_upscale_output_device", C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    ("iqpt_upscale_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_upscale_sync", C.c_int, [_P]),
+    ("iqpt_upscale_time", C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    ("iqpt_upscale_stats", C.c_int, [_P, _U64P, _U64P, _U64P]),
+]
+
 _lib = None
 
 
@@ -282,7 +309,8 @@ def load() -> C.CDLL:
     abi = lib.iqpt_abi_version() if getattr(lib, "iqpt_abi_version", None) is not None else None
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
-    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES + SVGF_SIGNATURES:
+    for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES + SVGF_SIGNATURES + \
+            UPSCALE_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:

@@ -1,0 +1,267 @@
+"""Guided upsampling's numpy reference (tests/upscale_ref.py) against the properties the definition
+implies, the entry points' argument checks that need no device, and its quality and tap classes on the CPU
+oracle's frames."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import denoise_ref as dr
+import oracle
+import upscale_ref as ur
+from iqpt import Scene, _lib, make_camera
+
+F = np.float32
+NO = ur.NO_PRIM
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def flat_guides(h, w, ident=0, z=0.5):
+    """One surface: the normal (0, 0, 1), one depth, one id."""
+    nz = np.zeros((h, w, 4), np.float32)
+    nz[..., 2] = 1.0
+    nz[..., 3] = z
+    return nz, np.full((h, w), ident, np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ properties
+@pytest.mark.parametrize("f", ur.FACTORS)
+def test_position_is_the_pixel_centre(f):
+    """x0 + fx is the hi pixel's centre in lo pixel units, (X + 1/2) / f - 1/2 (fx rounded once to binary32: half an ulp of a
+    value below 1 is 3e-8); fx is in [0, 1)."""
+    x0, fx = ur.position(8 * f, f)
+    assert fx.dtype == np.float32 and np.all((fx >= 0) & (fx < 1))
+    assert np.allclose(x0.astype(np.float64) + fx, (np.arange(8 * f) + 0.5) / f - 0.5, rtol=0, atol=3e-8)
+    assert x0[0] == -1 and x0[-1] == 7                  # one tap column off the frame at either border
+
+
+@pytest.mark.parametrize("f", ur.FACTORS)
+@pytest.mark.parametrize("value", [0.0, 0.5, 1.0])
+@pytest.mark.parametrize("params", [(5, 1024.0), (0, 0.0)])
+def test_constant_frame_comes_back_constant(f, value, params):
+    h, w = 5, 7
+    c = np.full((h, w, 4), value, np.float32)
+    c[..., 3] = 9.0                                      # the lo w is not used
+    nz_lo, id_lo = flat_guides(h, w)
+    nz_hi, id_hi = flat_guides(h * f, w * f)
+    out, bgra, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, f, *params)
+    want = np.zeros((h * f, w * f, 4), np.float32)
+    want[..., :3] = value
+    assert np.array_equal(bits(out), bits(want))         # class 0 is w = +0
+    assert counts == (h * f * w * f, 0, 0)
+    assert np.array_equal(bgra, dr.encode_bgra(want))
+
+
+@pytest.mark.parametrize("f", ur.FACTORS)
+def test_nothing_crosses_ids(f):
+    """Two surfaces, each with its own constant colour; the hi edge lies one and a half lo pixels right of the lo
+    edge, so some hi pixels find their id only in the widened stage."""
+    h, w = 6, 12
+    id_lo = np.zeros((h, w), np.uint32)
+    id_lo[:, 5:] = 4
+    id_hi = np.zeros((h * f, w * f), np.uint32)
+    id_hi[:, 5 * f + f + f // 2:] = 4
+    c = np.zeros((h, w, 4), np.float32)
+    c[id_lo == 0, :3] = 0.25
+    c[id_lo == 4, :3] = 1.0
+    nz_lo, _ = flat_guides(h, w)
+    nz_hi, _ = flat_guides(h * f, w * f)
+    out, _, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, f, 0, 0.0)   # every weight but the id test switched off
+    assert np.all(out[id_hi == 0][:, :3] == F(0.25)) and np.all(out[id_hi == 4][:, :3] == F(1.0))
+    assert counts[1] > 0 and counts[2] == 0 and counts[0] > counts[1]
+    assert np.all(out[..., 3] == np.where((id_hi == 0) & (np.arange(w * f)[None, :] >= 5 * f + f // 2), 1, 0))
+
+
+@pytest.mark.parametrize("f", ur.FACTORS)
+def test_nan_pixel_does_not_spread(f):
+    rng = np.random.default_rng(3)
+    h, w = 7, 9
+    c = rng.random((h, w, 4), dtype=np.float32)
+    c[3, 4] = [0.25, np.nan, 0.5, 7.0]
+    c[1, 1] = [np.inf, 0.1, 0.2, 0.0]
+    nz_lo, id_lo = flat_guides(h, w)
+    nz_hi, id_hi = flat_guides(h * f, w * f)
+    out, _, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    # at f = 3 a hi centre lies on each bad lo pixel (fx = fy = 0): its only weighted tap is gone, it is widened
+    lone = 2 if f == 3 else 0
+    assert np.all(np.isfinite(out)) and counts == (h * f * w * f - lone, lone, 0)
+    # the bad pixel is a removed tap: hi pixels whose four taps miss it are those of the clean frame
+    clean = c.copy()
+    clean[3, 4] = clean[1, 1] = 0.5
+    ref, _, _ = ur.upscale(clean, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    same = np.all(bits(out) == bits(ref), axis=2)
+    x0, _ = ur.position(w * f, f)
+    y0, _ = ur.position(h * f, f)
+    near = lambda py, px: ((y0[:, None] == py) | (y0[:, None] + 1 == py)) & ((x0[None, :] == px) | (x0[None, :] + 1 == px))
+    assert np.all(same[~(near(3, 4) | near(1, 1))]) and not np.all(same)
+    assert np.all((out[..., :3] >= 0) & (out[..., :3] <= 1))        # a weighted mean of the finite taps
+
+
+@pytest.mark.parametrize("f", ur.FACTORS)
+def test_absent_id_is_unguided_and_takes_the_nearest_bits(f):
+    rng = np.random.default_rng(5)
+    h, w = 6, 8
+    c = rng.random((h, w, 4), dtype=np.float32)
+    c.view(np.uint32)[2, 3, :3] = [0x7fc01234, 0xff800000, 0x80000000]      # a NaN's payload, -inf, -0: kept as bits
+    nz_lo, id_lo = flat_guides(h, w)
+    nz_hi, id_hi = flat_guides(h * f, w * f)
+    id_hi[2 * f:3 * f + 1, 3 * f:4 * f + 1] = 9                             # an id no lo pixel has
+    id_hi[0, 0] = 11
+    out, bgra, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    lost = id_hi != 0
+    assert counts == (int(np.sum(~lost)), 0, int(np.sum(lost)))
+    assert np.all(out[lost][:, 3] == 2) and np.all(out[~lost][:, 3] == 0)
+    yy, xx = np.nonzero(lost)
+    assert np.array_equal(bits(out)[yy, xx, :3], bits(c)[yy // f, xx // f, :3])
+    assert np.any(bits(out)[..., 0] == 0x7fc01234)
+    assert np.array_equal(bgra, dr.encode_bgra(out))
+
+
+@pytest.mark.parametrize("f", ur.FACTORS)
+def test_sky_is_bilinear_among_sky_pixels(f):
+    rng = np.random.default_rng(7)
+    h, w = 5, 6
+    c = rng.random((h, w, 4), dtype=np.float32)
+    nz_lo = np.full((h, w, 4), np.nan, np.float32)       # sky guides are never read into a weight
+    nz_hi = np.full((h * f, w * f, 4), np.nan, np.float32)
+    id_lo = np.full((h, w), NO, np.uint32)
+    id_hi = np.full((h * f, w * f), NO, np.uint32)
+    out, _, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    assert counts == (h * f * w * f, 0, 0) and np.all(np.isfinite(out))
+    x0, fx = ur.position(w * f, f)
+    y0, fy = ur.position(h * f, f)
+    for Y, X in ((f, f), (2 * f + 1, 3 * f - 1), (0, 0), (h * f - 1, w * f - 1), (0, 2 * f)):
+        num, den = np.zeros(3, np.float32), F(0)
+        for b in (0, 1):
+            for a in (0, 1):
+                g = (fy[Y] if b else F(1) - fy[Y]) * (fx[X] if a else F(1) - fx[X])
+                qx, qy = x0[X] + a, y0[Y] + b
+                if 0 <= qx < w and 0 <= qy < h and g > 0:
+                    num = num + g * c[qy, qx, :3]
+                    den = den + g
+        assert np.array_equal(bits(out[Y, X, :3]), bits(num / den)), (Y, X)
+    # in the frame's interior the four weights add up to 1: the plain bilinear value to rounding
+    Y, X = 2 * f + 1, 3 * f - 1
+    want = sum((fy[Y] if b else 1 - fy[Y]) * (fx[X] if a else 1 - fx[X]) * c[y0[Y] + b, x0[X] + a, :3].astype(np.float64)
+               for b in (0, 1) for a in (0, 1))
+    assert np.allclose(out[Y, X, :3], want, rtol=0, atol=1e-6)    # a dozen roundings of values below 1
+    # a surface in the lo frame gives nothing to a sky pixel, and the sky nothing to it
+    id_lo2 = id_lo.copy()
+    id_lo2[:, 3] = 2
+    c2 = c.copy()
+    c2[:, 3, :3] = 100.0
+    nz_lo2, _ = flat_guides(h, w)
+    out2, _, counts2 = ur.upscale(c2, nz_lo2, id_lo2, nz_hi, id_hi, f, 5, 1024.0)
+    assert np.all(out2[..., :3] <= 1.0) and counts2[2] == 0
+    assert (counts2[1] > 0) == (f == 3)                  # only there does a centre fall on a lo column: fx = 0
+
+
+def test_a_lone_lo_pixel_is_widened_only_through_the_depth_term():
+    """One lo pixel, f = 2: it is every hi pixel's one tap, with g = 0.5625 in stage A and 1 in stage B, and the weight
+    is rounded twice, g d first and then the quotient. With 1 + t t = 2 and d = 2^-148, stage A's RN(0.5625 d) = 2^-149
+    halves to a tie that goes to even, 0, while stage B's d / 2 = 2^-149: all four pixels are widened. With
+    1 + t t = 1 (s_z = 0) stage A's weight is RN(0.5625 d), zero only where d is: no d widens a pixel."""
+    c = np.array([[[1.0, 2.0, 3.0, 0.0]]], np.float32)     # whole multiples of the weight 2^-149 are exact
+    nz_lo, id_lo = flat_guides(1, 1)
+    nz_lo[0, 0, :3] = [1.0, 0.0, 0.0]
+    nz_hi, id_hi = flat_guides(2, 2, z=0.5 + 2.0 ** -10)
+    nz_hi[..., :3] = [2.0 ** -148, 0.0, 0.0]
+    out, _, counts = ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, 2, 0, 1024.0)
+    assert counts == (0, 4, 0) and np.array_equal(bits(out[..., :3]), bits(np.broadcast_to(c[0, 0, :3], (2, 2, 3))))
+    for d in (2.0 ** -149, 2.0 ** -148, 3 * 2.0 ** -149, 2.0 ** -126, 1.0):
+        nz_hi[..., 0] = d
+        assert ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, 2, 0, 0.0)[2] == (4, 0, 0), d
+    nz_hi[..., 0] = 0.0
+    assert ur.upscale(c, nz_lo, id_lo, nz_hi, id_hi, 2, 0, 0.0)[2] == (0, 0, 4)
+
+
+def test_argument_checks():
+    lib = _lib.load()
+    h = C.c_void_p()
+    for w, hh, f in ((0, 4, 2), (4, 0, 2), (8194, 4, 2), (4, 8194, 2), (8193, 3, 3), (4, 4, 1), (4, 4, 5), (4, 4, 0),
+                     (5, 4, 2), (4, 5, 2), (8, 8, 3), (6, 6, 4)):
+        assert lib.iqpt_upscale_create(0, w, hh, f, C.byref(h)) == 1 and not h.value, (w, hh, f)   # IQPT_ERR_INVALID_ARG
+        with pytest.raises(ValueError):
+            ur.check_args(w, hh, f)
+    assert lib.iqpt_upscale_create(0, 4, 4, 2, None) == 1
+    for w, hh, f in ((2, 2, 2), (8192, 8192, 4), (9, 3, 3)):
+        ur.check_args(w, hh, f)
+    good = _lib.UpscaleParams(5, 1024.0)
+    for bad in (_lib.UpscaleParams(8, 1.0), _lib.UpscaleParams(5, -1.0), _lib.UpscaleParams(5, float("nan"))):
+        assert lib.iqpt_upscale_set_params(None, C.byref(bad)) == 1
+        assert b"must be" in lib.iqpt_last_error()
+        with pytest.raises(ValueError):
+            ur.check_args(4, 4, 2, bad.normal_squarings, bad.depth_sharpness)
+    assert lib.iqpt_upscale_set_params(None, C.byref(good)) == 1 and b"NULL" in lib.iqpt_last_error()
+    assert lib.iqpt_upscale_set_params(None, None) == 1
+    assert lib.iqpt_upscale_default_params(None) == 1
+    p = _lib.UpscaleParams()
+    assert lib.iqpt_upscale_default_params(C.byref(p)) == 0 and (p.normal_squarings, p.depth_sharpness) == (5, 1024.0)
+    for call in (lambda: lib.iqpt_upscale_set_guides(None, None, None, None, None),
+                 lambda: lib.iqpt_upscale_set_guides_device(None, None, None, None, None),
+                 lambda: lib.iqpt_upscale_run(None, None), lambda: lib.iqpt_upscale_run_device(None, None),
+                 lambda: lib.iqpt_upscale_frame(None, None, None, None), lambda: lib.iqpt_upscale_read(None, None, None),
+                 lambda: lib.iqpt_upscale_output_device(None, None), lambda: lib.iqpt_upscale_sync(None),
+                 lambda: lib.iqpt_upscale_copy_frame_device(None, None, 0), lambda: lib.iqpt_upscale_time(None, None, None),
+                 lambda: lib.iqpt_upscale_stats(None, None, None, None)):
+        assert call() == 1
+    assert lib.iqpt_upscale_destroy(None) == 0
+    with pytest.raises(ValueError):                       # a lo frame that is not the hi frame over the factor
+        ur.upscale(np.zeros((3, 3, 4), F), *flat_guides(3, 3), *flat_guides(6, 8), 2, 5, 1024.0)
+
+
+# ------------------------------------------------------------------------------------------------ quality
+W, H = 96, 54
+# r measured with this reference (DESIGN.md §14 "Quality"); the test asks for half of that gain
+R_MEASURED = 0.7369     # raw hi 4 spp RMSE 0.0937, lo 16 spp upsampled 0.0690
+
+
+def camera_matrices(cam):
+    return np.array(cam.view, np.float32).view(np.uint32), np.array(cam.projection, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("w,h", [(48, 27), (32, 18)])
+def test_camera_matrices_do_not_depend_on_the_size(w, h):
+    """What iqpt_upscale_frame requires of its two rasterizers holds for make_camera at any two sizes."""
+    hi, lo = camera_matrices(make_camera(W, H)), camera_matrices(make_camera(w, h))
+    assert np.array_equal(hi[0], lo[0]) and np.array_equal(hi[1], lo[1])
+
+
+def test_quality_and_classes_on_the_oracle_frames():
+    """cornell_lit, hi 96x54, depth 8, seed 1984, q = 5, s_z = 1024: RMSE over xyz against the oracle's 2048-spp hi
+    frame, the lo 48x27 frame at 16 spp (the rays of 4 spp at the hi size) upsampled by 2 over the raw 4-spp hi
+    frame; and the shares of the widened and unguided classes, which are capped."""
+    f, w, h = 2, W // 2, H // 2
+    sc = Scene()
+    sc.add_preset("cornell_lit")
+    pk = sc.build_packet()
+    cam_hi, cam_lo = make_camera(W, H), make_camera(w, h)
+    fr = oracle.OracleFrame(W, H, max_depth=8, seed=1984)
+    fr.render(pk, cam_hi, 4)
+    noisy = fr.lin.copy().reshape(H, W, 4)
+    fr.render(pk, cam_hi, 2044)
+    ref = fr.lin.reshape(H, W, 4)[..., :3].astype(np.float64)
+    lo = oracle.OracleFrame(w, h, max_depth=8, seed=1984)
+    lo.render(pk, cam_lo, 4)
+    lo4 = lo.lin.copy().reshape(h, w, 4)
+    lo.render(pk, cam_lo, 12)
+    lo16 = lo.lin.copy().reshape(h, w, 4)
+    nz_hi, id_hi = dr.gbuffer_scene(sc.draw_list(), cam_hi, W, H)
+    nz_lo, id_lo = dr.gbuffer_scene(sc.draw_list(), cam_lo, w, h)
+
+    def rmse(a):
+        return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - ref) ** 2)))
+
+    up4, _, _ = ur.upscale(lo4, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    up16, _, counts = ur.upscale(lo16, nz_lo, id_lo, nz_hi, id_hi, f, 5, 1024.0)
+    raw, e4, e16 = rmse(noisy), rmse(up4), rmse(up16)
+    r = e16 / raw
+    shares = [n / (W * H) for n in counts]
+    print(f"raw hi 4 spp RMSE {raw:.4f}; lo 4 spp upsampled {e4:.4f}; lo 16 spp upsampled {e16:.4f}, r = {r:.4f}; "
+          f"guided {shares[0]:.5f} widened {shares[1]:.5f} unguided {shares[2]:.5f}; sky {np.mean(id_hi == NO):.3f}")
+    assert sum(counts) == W * H
+    assert shares[2] <= 0.01 and shares[1] <= 0.02
+    assert r <= (1 + R_MEASURED) / 2

@@ -1,0 +1,164 @@
+"""What a frame costs through guided upsampling, next to the full-size trace it stands in for.
+
+One config (C2 by default: the Cornell box at 1920x1080, 64 spp, 8 bounces) in one process. A path tracer and a
+rasterizer of the full size, and for every factor f a path tracer and a rasterizer of 1/f size and an upscaler; all
+are made and warmed up first. Then --runs rounds; every round takes, in turn, one full-size step and one step of
+every factor, so that whatever else the machine does meets all of them alike. A full-size step is one iqpt_render
+launch of --spp samples. A step of factor f is: the lo launch of the same spp, both G-buffer passes (recomputed:
+the camera is set again) and the upscale kernel. Every part is timed by the library's own HIP events (render
+kernel span, G-buffer pass, upscale kernel), and the whole step by the host clock from the first call to the
+upscaler's synchronise. Reported are the median over the rounds with minimum and maximum, and per factor the ratio
+of medians to the full-size launch of the same job. Nothing is compared across jobs. Needs the GPU; prints one JSON
+line and, with --out, writes it to a file.
+
+    python tools/upscale_bench.py --config c2 --factors 2,4 --runs 30 --out profiles/r10/upscale_bench_c2.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "path-tracer-and-rasterizer-engine_amd"))
+import iqpt  # noqa: E402
+from iqpt.scene import CONFIGS, Scene, make_camera  # noqa: E402
+from iqpt.upscale import default_params  # noqa: E402
+
+
+def spread(v):
+    return {"median": float(statistics.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+
+class Full:
+    """The yardstick: the path tracer at the full size."""
+
+    def __init__(self, sc, pk, w, h, max_depth, spp):
+        self.pt = iqpt.PathTracer(w, h, max_depth=max_depth)
+        self.pt.set_camera(make_camera(w, h))
+        self.pt.upload_packet(pk)
+        self.pt.prepare()
+        self.spp = spp
+        self.rows = {"trace_kernel": [], "step_wall": []}
+
+    def step(self, keep):
+        t0 = time.perf_counter()
+        self.pt.render(self.spp)
+        self.pt.sync()
+        wall = 1e3 * (time.perf_counter() - t0)
+        ms, n = self.pt.kernel_time()
+        assert n == 1
+        if keep:
+            self.rows["trace_kernel"].append(ms)
+            self.rows["step_wall"].append(wall)
+
+    def close(self):
+        self.pt.close()
+
+
+class Upscaled:
+    """The lo path tracer, the two rasterizers and the upscaler of one factor."""
+
+    def __init__(self, sc, pk, w, h, f, max_depth, spp, params):
+        self.f, self.spp = f, spp
+        self.cam_lo, self.cam_hi = make_camera(w // f, h // f), make_camera(w, h)
+        self.pt = iqpt.PathTracer(w // f, h // f, max_depth=max_depth)
+        self.pt.set_camera(self.cam_lo)
+        self.pt.upload_packet(pk)
+        self.pt.prepare()
+        self.r_lo = iqpt.Rasterizer(w // f, h // f, samples=1)
+        self.r_hi = iqpt.Rasterizer(w, h, samples=1)
+        for r in (self.r_lo, self.r_hi):
+            r.upload_scene(sc)
+        self.up = iqpt.Upscaler(w, h, f)
+        self.up.set_params(params["normal_squarings"], params["depth_sharpness"])
+        self.rows = {k: [] for k in ("trace_kernel", "gbuffer_lo", "gbuffer_hi", "upscale_kernel", "parts_sum", "step_wall")}
+        self.stats = None
+
+    def step(self, keep):
+        t0 = time.perf_counter()
+        self.pt.render(self.spp)
+        self.r_lo.set_camera(self.cam_lo)               # a camera set again: both passes are recomputed
+        self.r_hi.set_camera(self.cam_hi)
+        self.up.frame(self.pt, self.r_lo, self.r_hi)
+        self.up.sync()
+        wall = 1e3 * (time.perf_counter() - t0)
+        ker, n = self.pt.kernel_time()
+        g_lo, n_lo = self.r_lo.gbuffer_time()
+        g_hi, n_hi = self.r_hi.gbuffer_time()
+        ups, n_up = self.up.time()
+        assert (n, n_lo, n_hi, n_up) == (1, 1, 1, 1)
+        if keep:
+            for k, v in (("trace_kernel", ker), ("gbuffer_lo", g_lo), ("gbuffer_hi", g_hi), ("upscale_kernel", ups),
+                         ("parts_sum", ker + g_lo + g_hi + ups), ("step_wall", wall)):
+                self.rows[k].append(v)
+            self.stats = self.up.stats()
+
+    def close(self):
+        for o in (self.up, self.r_hi, self.r_lo, self.pt):
+            o.close()
+
+
+def bench(cfg, w, h, spp, max_depth, factors, warmup, runs):
+    sc = Scene()
+    sc.add_preset(cfg.preset)
+    pk = sc.build_packet()
+    params = default_params()
+    full = Full(sc, pk, w, h, max_depth, spp)
+    ups = [Upscaled(sc, pk, w, h, f, max_depth, spp, params) for f in factors]
+    try:
+        for k in range(warmup + runs):
+            for o in [full] + ups:
+                o.step(k >= warmup)
+        full_ms = statistics.median(full.rows["trace_kernel"])
+        out = {"config": cfg.name, "scene": cfg.preset, "width": w, "height": h, "spp": spp, "max_depth": max_depth,
+               "runs": runs, "warmup": warmup, **params,
+               "full": {k: spread(v) for k, v in full.rows.items()}, "factors": {}}
+        for u in ups:
+            row = {k: spread(v) for k, v in u.rows.items()}
+            row["lo_width"], row["lo_height"] = w // u.f, h // u.f
+            row["guided"], row["widened"], row["unguided"] = u.stats
+            row["parts_sum_over_full_trace"] = row["parts_sum"]["median"] / full_ms
+            row["step_wall_over_full_step_wall"] = row["step_wall"]["median"] / statistics.median(full.rows["step_wall"])
+            out["factors"][str(u.f)] = row
+        return out
+    finally:
+        for o in [full] + ups:
+            o.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--width", type=int, default=0, help="the full frame (default: the config's)")
+    ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--spp", type=int, default=0, help="samples per launch at either size (default: the config's)")
+    ap.add_argument("--factors", default="2,4")
+    ap.add_argument("--runs", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--lib", default="", help="A/B only: load this prebuilt libiqpt")
+    a = ap.parse_args()
+    if a.runs < 20:
+        ap.error("--runs must be at least 20")
+    if a.lib:
+        from iqpt import _lib
+        _lib.LIB_PATH = Path(a.lib).resolve()
+    cfg = CONFIGS[a.config]
+    w, h, spp = a.width or cfg.width, a.height or cfg.height, a.spp or cfg.spp
+    factors = [int(f) for f in a.factors.split(",")]
+    for f in factors:
+        if f not in (2, 3, 4) or w % f or h % f:
+            ap.error(f"factor {f} must be 2, 3 or 4 and divide {w}x{h}")
+    line = json.dumps(bench(cfg, w, h, spp, cfg.max_depth, factors, a.warmup, a.runs))
+    print(line, flush=True)
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -154,6 +154,14 @@ typedef struct iqpt_ctx iqpt_ctx;
 int iqpt_camera_init(iqpt_camera* cam, uint16_t width, uint16_t height, float fovh_deg,
                      float znear, float zfar, const float position[4], const float forward[4]);
 
+/* The camera to hand the path tracer when its frame is joined, pixel by pixel, with the rasterizer's planes of
+ * `cam` (no reference counterpart: the reference's two renderers are separate views). get_ray
+ * centres pixel (x, y)'s sample square on (x, y) (camera.cu:24-25), the rasterizer samples (x + 1/2, y + 1/2).
+ * `out` is `cam` with inv_proj = T * inv_proj and projection = projection * T^-1, T adding (1/W, -1/H) to an NDC
+ * point, so that the path tracer's pixel samples the square centred on (x + 1/2, y + 1/2) of `cam`; every other
+ * field is copied. `out` may be `cam`. Host only. */
+int iqpt_camera_align(const iqpt_camera* cam, iqpt_camera* out);
+
 /* Creates a render context on HIP device `device` for a width x height frame. `pixels` selects
  * the owned subset (NULL = the whole frame). Allocates the accumulator (float4), the BGRA8 frame
  * and the per-pixel XORWOW states and runs the RNG init kernel: curand_init(seed, pixelid, 0). */

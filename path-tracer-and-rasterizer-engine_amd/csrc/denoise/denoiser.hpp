@@ -34,7 +34,8 @@ public:
     denoiser& operator=(const denoiser&) = delete;
 
     void set_params(const iqpt_denoise_params& p) { IQPT_THROW_FAILED(iqpt_denoise_set_params(m_d, &p)); }
-    // the path tracer's accumulator under the rasterizer's G-buffer, filtered and read back into host_pixels()
+    // the path tracer's accumulator under the rasterizer's G-buffer, filtered and read back into host_pixels(); the
+    // context's camera is the aligned one of the rasterizer's (camera::aligned())
     void frame(iqpt_ctx* ctx, iqpt_raster* raster) {
         IQPT_THROW_FAILED(iqpt_denoise_frame(m_d, ctx, raster));
         IQPT_THROW_FAILED(iqpt_denoise_read(m_d, nullptr, reinterpret_cast<uint8_t*>(m_host_pixels.data())));

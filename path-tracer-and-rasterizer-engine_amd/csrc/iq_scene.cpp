@@ -499,4 +499,23 @@ int iqpt_camera_init(iqpt_camera* cam, uint16_t width, uint16_t height, float fo
     return IQPT_OK;
 }
 
+// the path tracer's pixel (x, y) samples x_ndc = ((x + j) / W) * 2 - 1, a square centred on the
+// pixel's integer corner; the rasterizer samples pixel centres. T adds (1/W, -1/H) to an NDC point (row vectors:
+// T is the identity with row 3 = (1/W, -1/H, 0, 1)), inv_proj' = T * inv_proj and projection' = projection * T^-1,
+// written out entry by entry so the float operations are the normative ones.
+int iqpt_camera_align(const iqpt_camera* cam, iqpt_camera* out) {
+    if (!cam || !out || cam->width == 0 || cam->height == 0)
+        return iqpt::fail(IQPT_ERR_INVALID_ARG, "bad camera arguments");
+    iqpt_camera r = *cam;
+    const float sx = 1.0f / (float)cam->width, sy = 1.0f / (float)cam->height;
+    for (int j = 0; j < 4; ++j)
+        r.inv_proj[12 + j] = (cam->inv_proj[12 + j] + sx * cam->inv_proj[j]) - sy * cam->inv_proj[4 + j];
+    for (int i = 0; i < 4; ++i) {
+        r.projection[4 * i + 0] = cam->projection[4 * i + 0] - cam->projection[4 * i + 3] * sx;
+        r.projection[4 * i + 1] = cam->projection[4 * i + 1] + cam->projection[4 * i + 3] * sy;
+    }
+    *out = r;
+    return IQPT_OK;
+}
+
 }  // extern "C"

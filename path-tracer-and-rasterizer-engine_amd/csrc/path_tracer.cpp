@@ -81,11 +81,16 @@ path_tracer::path_tracer(camera* cam, const path_tracer_options& opt) : m_camera
         IQPT_THROW_FAILED(iqpt_comm_init(m_ctx, opt.rank, opt.world, opt.comm_id.data(), opt.comm_id.size()));
         m_comm = true;
     }
-    IQPT_THROW_FAILED(iqpt_set_camera(m_ctx, &cam->raw()));
+    update_camera();
     m_host_pixels.assign((size_t)w * h, pixel{0, 0, 0, 0});              // path_tracer.cu:130-131
 }
 
 path_tracer::~path_tracer() { iqpt_destroy(m_ctx); }
+
+void path_tracer::update_camera() {
+    const iqpt_camera cam = m_opt.align_camera ? m_camera->aligned() : m_camera->raw();
+    IQPT_THROW_FAILED(iqpt_set_camera(m_ctx, &cam));
+}
 
 void path_tracer::begin_frame() {}
 

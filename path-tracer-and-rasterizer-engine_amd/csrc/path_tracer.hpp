@@ -61,6 +61,13 @@ public:
     uint16_t get_width() const { return m_cam.width; }
     uint16_t get_height() const { return m_cam.height; }
     const iqpt_camera& raw() const { return m_cam; }
+    // the camera the path tracer takes when its pixels are joined with the rasterizer's planes of raw()
+    // (iqpt_camera_align)
+    iqpt_camera aligned() const {
+        iqpt_camera a;
+        IQPT_THROW_FAILED(iqpt_camera_align(&m_cam, &a));
+        return a;
+    }
 
 private:
     iqpt_camera m_cam;
@@ -114,6 +121,9 @@ struct path_tracer_options {
     float launch_interval = 0.1f;                // path_tracer.cu:378
     uint32_t spp_per_launch = 1;                 // one sample per reference launch
     std::string ppm_path;                        // headless present target ("" = none)
+    // the context gets camera::aligned() instead of camera::raw(): pixel (x, y) samples the square centred on the
+    // rasterizer's pixel centre. iqpt::renderer turns it on with any of its post-process blocks.
+    bool align_camera = false;
     // multi-GPU (one process per GPU): this process renders rank's cyclic rows of the frame and the present
     // path gathers the frame to rank 0 over RCCL (iqpt_comm_init / iqpt_gather_read). comm_id: the bytes of
     // path_tracer::comm_unique_id() from one rank, shared out of band; empty = single GPU.
@@ -138,6 +148,9 @@ public:
     void end_frame() override;
     void draw_scene(const scene& scene, std::vector<shader>& shaders, float dt) override;
     void reset() { m_pending_reset = true; }                              // path_tracer.h:35
+    // hands the camera object's present matrices to the context (aligned under path_tracer_options::align_camera):
+    // for a caller that changed the camera in place
+    void update_camera();
 
     // headless extensions; with a communicator the host frame is the whole gathered frame on rank 0
     const std::vector<pixel>& host_pixels() const { return m_host_pixels; }

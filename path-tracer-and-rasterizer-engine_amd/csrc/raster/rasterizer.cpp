@@ -86,7 +86,10 @@ void rasterizer::draw_scene(const scene& scn, std::vector<shader>& shaders, floa
 void renderer::init(camera* cam, const renderer_options& opt) {                  // renderer.cu:18-26
     if (!g_renderer) {
         rasterizer::init(cam, opt.rasterizer);
-        path_tracer::init(cam, opt.path_tracer);
+        // a block joins the path tracer's pixels with the rasterizer's planes: the aligned camera
+        path_tracer_options pto = opt.path_tracer;
+        if (opt.denoise.enabled || opt.temporal.enabled || opt.svgf.enabled) pto.align_camera = true;
+        path_tracer::init(cam, pto);
         g_renderer = new renderer(cam, opt);
     }
 }

@@ -54,6 +54,8 @@ private:
 };
 
 struct renderer_options {
+    // with denoise, temporal or svgf enabled the path tracer runs under camera::aligned() (align_camera is forced
+    // on), the rasterizer and the blocks under camera::raw(): DESIGN.md §9.7
     path_tracer_options path_tracer;
     rasterizer_options rasterizer;
     // enabled: end_frame under the path-tracing engine also filters the accumulator under the rasterizer's

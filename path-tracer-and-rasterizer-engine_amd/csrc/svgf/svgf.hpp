@@ -35,7 +35,8 @@ public:
     svgf& operator=(const svgf&) = delete;
 
     void set_params(const iqpt_svgf_params& p) { IQPT_THROW_FAILED(iqpt_svgf_set_params(m_s, &p)); }
-    // a new view from the rasterizer's G-buffer; cam is the camera the rasterizer has, kept for same_view()
+    // a new view from the rasterizer's G-buffer; cam is the camera the rasterizer has (the plain one: the path
+    // tracer's is its aligned form), kept for same_view()
     void begin_view(iqpt_raster* raster, const iqpt_camera& cam) {
         IQPT_THROW_FAILED(iqpt_svgf_begin_view_raster(m_s, raster));
         m_camera = cam;

@@ -35,7 +35,8 @@ public:
     temporal& operator=(const temporal&) = delete;
 
     void set_params(const iqpt_temporal_params& p) { IQPT_THROW_FAILED(iqpt_temporal_set_params(m_t, &p)); }
-    // a new view from the rasterizer's G-buffer; cam is the camera the rasterizer has, kept for same_view()
+    // a new view from the rasterizer's G-buffer; cam is the camera the rasterizer has (the plain one: the path
+    // tracer's is its aligned form), kept for same_view()
     void begin_view(iqpt_raster* raster, const iqpt_camera& cam) {
         IQPT_THROW_FAILED(iqpt_temporal_begin_view_raster(m_t, raster));
         m_camera = cam;

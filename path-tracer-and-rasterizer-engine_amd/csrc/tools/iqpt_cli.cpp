@@ -141,7 +141,8 @@ int main(int argc, char** argv) {
             {
                 iqpt::upscaler up(W, H, (uint32_t)upscale, device);
                 const iqpt_packet_desc pk = scn.build_packet();
-                IQPT_THROW_FAILED(iqpt_set_camera(ctx, &cam_lo.raw()));
+                const iqpt_camera pt_cam = cam_lo.aligned();
+                IQPT_THROW_FAILED(iqpt_set_camera(ctx, &pt_cam));
                 IQPT_THROW_FAILED(iqpt_upload_packet(ctx, &pk));
                 IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_lo, scn.handle()));
                 IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_hi, scn.handle()));
@@ -190,7 +191,9 @@ int main(int argc, char** argv) {
                     pos[0] = pos[0] + step_x * (float)k;
                     IQPT_THROW_FAILED(iqpt_camera_init(&moved, (uint16_t)width, (uint16_t)height, cam.raw().fovh, 0.01f, 100.0f,
                                                        pos, cam.raw().forward));
-                    IQPT_THROW_FAILED(iqpt_set_camera(ctx, &moved));
+                    iqpt_camera pt_cam;
+                    IQPT_THROW_FAILED(iqpt_camera_align(&moved, &pt_cam));
+                    IQPT_THROW_FAILED(iqpt_set_camera(ctx, &pt_cam));
                     IQPT_THROW_FAILED(iqpt_reset(ctx));
                     IQPT_THROW_FAILED(iqpt_raster_set_camera(rs, &moved));
                     if (tmp) tmp->begin_view(rs, moved);

@@ -56,7 +56,10 @@ int main(int argc, char** argv) {
         {
             iqpt::scene scn;
             scn.add_preset("cornell_lit");
-            iqpt::renderer::init(&cam, opt);
+            // (under the aligned camera, which the renderer gives the path tracer by itself with a block on)
+            iqpt::renderer_options off = opt;
+            off.path_tracer.align_camera = true;
+            iqpt::renderer::init(&cam, off);
             iqpt::renderer* r = iqpt::renderer::get();
             CHECK(r && !r->get_denoiser());
             run(r, scn, shaders);

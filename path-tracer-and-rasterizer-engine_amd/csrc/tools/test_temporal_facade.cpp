@@ -72,7 +72,10 @@ int main(int argc, char** argv) {
         {
             iqpt::scene scn;
             scn.add_preset("cornell_lit");
-            iqpt::renderer::init(&cam, opt);
+            // (under the aligned camera, which the renderer gives the path tracer by itself with a block on)
+            iqpt::renderer_options off = opt;
+            off.path_tracer.align_camera = true;
+            iqpt::renderer::init(&cam, off);
             iqpt::renderer* r = iqpt::renderer::get();
             CHECK(r && !r->get_temporal() && !r->get_denoiser());
             run(r, scn, shaders, kLaunchesA);
@@ -119,7 +122,7 @@ int main(int argc, char** argv) {
 
             // camera B (another field of view) and a reset: a second view that inherits A's samples
             cam = iqpt::camera(w, h, 50.0f);
-            IQPT_THROW_FAILED(iqpt_set_camera(pt->context(), &cam.raw()));
+            pt->update_camera();                 // the aligned form: the renderer turned align_camera on
             r->reset();
             run(r, scn, shaders, kLaunchesB);
             CHECK(pt->frames() == (uint64_t)kLaunchesB);

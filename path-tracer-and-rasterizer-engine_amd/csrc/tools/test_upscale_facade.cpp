@@ -38,7 +38,8 @@ int main(int argc, char** argv) {
         IQPT_THROW_FAILED(iqpt_raster_create(0, w, h, 1, &r_lo));
         IQPT_THROW_FAILED(iqpt_raster_create(0, W, H, 1, &r_hi));
         const iqpt_packet_desc pk = scn.build_packet();
-        IQPT_THROW_FAILED(iqpt_set_camera(ctx, &cam_lo.raw()));
+        const iqpt_camera pt_cam = cam_lo.aligned();
+        IQPT_THROW_FAILED(iqpt_set_camera(ctx, &pt_cam));
         IQPT_THROW_FAILED(iqpt_upload_packet(ctx, &pk));
         IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_lo, scn.handle()));
         IQPT_THROW_FAILED(iqpt_raster_upload_scene(r_hi, scn.handle()));

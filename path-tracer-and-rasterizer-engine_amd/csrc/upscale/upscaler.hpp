@@ -34,7 +34,8 @@ public:
 
     void set_params(const iqpt_upscale_params& p) { IQPT_THROW_FAILED(iqpt_upscale_set_params(m_u, &p)); }
     // the lo path tracer's accumulator under the two rasterizers' G-buffers, upsampled and read back into
-    // host_pixels()
+    // host_pixels(); the context's camera is the aligned one of the lo rasterizer's (camera::aligned(), DESIGN.md
+    // §9.7), the two rasterizers' are plain
     void frame(iqpt_ctx* ctx, iqpt_raster* raster_lo, iqpt_raster* raster_hi) {
         IQPT_THROW_FAILED(iqpt_upscale_frame(m_u, ctx, raster_lo, raster_hi));
         IQPT_THROW_FAILED(iqpt_upscale_read(m_u, nullptr, reinterpret_cast<uint8_t*>(m_host_pixels.data())));

@@ -8,7 +8,7 @@ from ._lib import (DEFAULT_MAX_DEPTH, DEFAULT_SEED, MAT_EMISSIVE, MAT_OREN_NAYAR
 from .denoise import Denoiser  # noqa: F401
 from .raster import Rasterizer  # noqa: F401
 from .render import PathTracer, comm_unique_id, kernel_name, pixel_set, write_ppm  # noqa: F401
-from .scene import CONFIGS, Config, Scene, config_scene, make_camera, packet_stats  # noqa: F401
+from .scene import CONFIGS, Config, Scene, align_camera, config_scene, make_camera, packet_stats  # noqa: F401
 from .svgf import Svgf  # noqa: F401
 from .temporal import Temporal  # noqa: F401
 from .upscale import Upscaler  # noqa: F401

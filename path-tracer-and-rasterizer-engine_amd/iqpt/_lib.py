@@ -99,6 +99,7 @@ _P = C.c_void_p
 _FP = C.POINTER(C.c_float)
 SIGNATURES = [
     ("iqpt_camera_init", C.c_int, [C.POINTER(Camera), C.c_uint16, C.c_uint16, C.c_float, C.c_float, C.c_float, _FP, _FP]),
+    ("iqpt_camera_align", C.c_int, [C.POINTER(Camera), C.POINTER(Camera)]),
     ("iqpt_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(PixelSet), C.c_uint64, C.c_int, C.POINTER(_P)]),
     ("iqpt_destroy", C.c_int, [_P]),
     ("iqpt_set_camera", C.c_int, [_P, C.POINTER(Camera)]),

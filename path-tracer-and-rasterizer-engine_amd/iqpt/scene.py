@@ -127,6 +127,14 @@ def make_camera(width: int, height: int, fovh: float = 45.0, znear: float = 0.01
     return cam
 
 
+def align_camera(cam: Camera) -> Camera:
+    """iqpt_camera_align: the camera to give the path tracer when its pixels are joined with the
+    rasterizer's planes of ``cam``: pixel (x, y) then samples the square centred on (x + 1/2, y + 1/2) of ``cam``."""
+    out = Camera()
+    check(_lib.load().iqpt_camera_align(C.byref(cam), C.byref(out)), "iqpt_camera_align")
+    return out
+
+
 def packet_stats(pk: PacketDesc) -> dict:
     """T (triangle instances, Σ over drawcalls of num_indices/3) and S (sphere drawcalls)."""
     t = 0

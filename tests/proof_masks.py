@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from iqpt import MAT_EMISSIVE, MAT_OREN_NAYAR, Scene, _lib, make_camera
+from iqpt import MAT_EMISSIVE, MAT_OREN_NAYAR, Scene, _lib, align_camera, make_camera
 from test_certain import Footprint, certain_tile, covering, facing_camera, loguni
 from test_cull import corner_rays, cull_tile
 
@@ -214,8 +214,9 @@ def cameras(w, h):
     intervals are wide. A tile's bundle is a box of directions about as wide as the tile, so it culls a small
     primitive only at an angle of about sqrt(2 x that width) from it: several tiles for the 45 and 70 degree cameras,
     more tiles than these frames have for the 5 degree one (whose masks stay full) and the 120 degree one (whose
-    tiles span 24 degrees)."""
-    return [
+    tiles span 24 degrees). Then the aligned form of each (iqpt_camera_align), in the same order:
+    inv_proj[12] and inv_proj[13] are non-zero, which no camera of iqpt_camera_init has."""
+    plain = [
         ("default", make_camera(w, h)),
         ("fov5", make_camera(w, h, fovh=5.0, position=(0.5, 0.2, -3.0, 0.0), forward=(0.1, 0.05, 1.0, 0.0))),
         ("pitched", make_camera(w, h, fovh=70.0, znear=0.05, zfar=50.0, position=(0.3, 1.2, -2.0, 0.0),
@@ -224,8 +225,13 @@ def cameras(w, h):
                                forward=(0.7, -0.2, -0.6, 0.0))),
         ("far", make_camera(w, h, position=(8000.0, -2500.0, 5500.0, 0.0), forward=(0.3, -0.2, 1.0, 0.0))),
     ]
+    return plain + [(name + "_aligned", align_camera(cam)) for name, cam in plain]
 
 
+N_PLAIN = 5                # cameras(w, h)[k] and [N_PLAIN + k] are a camera and its aligned form
+
+
+# (k below: the scene's index in its family, the camera's index within its group of N_PLAIN)
 STREAMED = (1, 4)          # the scenes of the "tris" family with two balls (more than 32 KiB of pair records)
 FILLED = 3                 # the scene that gets the triangle covering the frame and the sphere around the camera
 

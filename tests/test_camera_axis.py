@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from iqpt import _lib, make_camera
+from iqpt import _lib, align_camera, make_camera
 
 f32 = np.float32
 
@@ -103,6 +103,25 @@ def test_pitch_cameras_bit_identical(pitch, pos):
     if pos[0] == 0.0 and pitch == 0.0:
         # x_ndc = +-0 rays have zero x components: the zero signs must agree too (checked above)
         assert np.any(g[:, 0] == 0.0)
+
+
+@pytest.mark.parametrize("size", [(1920, 1080), (17, 13), (1, 1), (300, 7)])
+@pytest.mark.parametrize("pitch", [-0.5, 0.0, 1.7])
+def test_aligned_cameras_qualify_and_are_bit_identical(pitch, size):
+    """iqpt_camera_align leaves the zero pattern and the constant w in place and makes P[12], P[13]
+    non-zero, which no camera of iqpt_camera_init has: the last addends of the x and y chains now decide more than
+    the sign of a zero."""
+    plain = pitch_camera(*size, pitch, fovh=60.0)
+    cam = align_camera(plain)
+    ok, k = cam_axis(cam)
+    assert ok
+    P, _ = mats(cam)
+    assert P[3, 0] != 0 and P[3, 1] != 0 and k[2] == P[3, 0] and k[3] == P[3, 1]
+    assert np.array_equal(k[[0, 1, 4, 5]], cam_axis(plain)[1][[0, 1, 4, 5]])     # the same scales and 1 / w
+    g = assert_same_bits(cam)
+    assert not np.array_equal(g.view(np.uint32), assert_same_bits(plain).view(np.uint32))
+    yaw = align_camera(make_camera(*size, position=(0.0, 0.5, -3.0, 0.0), forward=(0.4, -0.5, 3.0, 0.0)))
+    assert not cam_axis(yaw)[0]
 
 
 def test_degenerate_columns_bit_identical():

@@ -9,7 +9,7 @@ import pytest
 
 import oracle
 from helpers import compare
-from iqpt import PathTracer, Scene, _lib, make_camera
+from iqpt import PathTracer, Scene, _lib, align_camera, make_camera
 from test_camera_axis import cam_axis, general, mats, ndc_samples, pitch_camera
 
 pytestmark = pytest.mark.gpu
@@ -41,9 +41,16 @@ def last_options(pt):
     return o.value
 
 
-@pytest.mark.parametrize("which", ["reference", "pitch_up", "origin", "degenerate"])
+@pytest.mark.parametrize("which", ["reference", "pitch_up", "origin", "degenerate", "reference_aligned",
+                                   "pitch_up_aligned", "small_aligned"])
 def test_device_camera_transforms_bit_identical(require_gpu, which):
-    if which == "reference":
+    if which == "reference_aligned":         # P[12], P[13] non-zero
+        cam = align_camera(make_camera(1920, 1080))
+    elif which == "pitch_up_aligned":
+        cam = align_camera(pitch_camera(320, 200, 1.7, (0.0, -2.0, 4.0), fovh=60.0))
+    elif which == "small_aligned":
+        cam = align_camera(make_camera(17, 13))
+    elif which == "reference":
         cam = make_camera(1920, 1080)
     elif which == "pitch_up":
         cam = pitch_camera(320, 200, 1.7, (0.0, -2.0, 4.0), fovh=60.0)

@@ -17,7 +17,7 @@ import denoise_ref as dr
 import iqpt
 import oracle
 import raster_ref as rr
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 NO = dr.NO_PRIM
@@ -187,7 +187,7 @@ def test_frame_end_to_end(require_gpu):
     cam = make_camera(W, H)
     params = (3, 5, 1024.0, 2.0)
     with PathTracer(W, H, max_depth=depth) as pt, Rasterizer(W, H) as r, Denoiser(W, H) as d:
-        pt.set_camera(cam)
+        pt.set_camera(align_camera(cam))                  # the path tracer's camera is the aligned one
         pt.upload_packet(pk)
         pt.render(spp)
         r.set_camera(cam)
@@ -202,7 +202,7 @@ def test_frame_end_to_end(require_gpu):
         assert_gbuffer((nz, ids), gbuffer_ref("cornell_lit"), "cornell_lit")
         # the path tracer is untouched: its frame still equals the oracle bit for bit
         fr = oracle.OracleFrame(W, H, max_depth=depth)
-        fr.render(pk, cam, spp)
+        fr.render(pk, align_camera(cam), spp)
         assert np.array_equal(bits(acc), bits(fr.lin)) and np.array_equal(acc_bgra, fr.bgra)
         # the filter did something, and the same call again gives the same bits
         guided = ids != NO

@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, _build, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, _build, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,7 @@ def both_frames(preset, w, h, launches, spp, depth, params=None):
     sc.add_preset(preset)
     cam = make_camera(w, h)
     with PathTracer(w, h, max_depth=depth) as pt, Rasterizer(w, h) as r, Denoiser(w, h) as d:
-        pt.set_camera(cam)
+        pt.set_camera(align_camera(cam))                  # what the renderer and the CLI give it
         pt.upload_packet(sc.build_packet())
         for _ in range(launches):
             pt.render(spp)

@@ -93,6 +93,12 @@ def render(preset, w, h, launches, depth=8, crop=None, overlap=True, stats=False
         lb.iqpt_debug_read_stats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         opt = lb.iqpt_debug_default_options() | K_OPT_PRIO | K_OPT_STATS | K_OPT_PIPE
         _lib.check(lb.iqpt_debug_set_kernel_options(pt._h, opt), "iqpt_debug_set_kernel_options")
+        # The counters compared between two libraries are per wave, so they are a function of the frame only while a
+        # wave's pixels are one tile's. With the default refill (one idle lane) a wave that starts early takes lanes of
+        # the next tile from the queue while its own still run, which depends on when the waves of a cold first launch
+        # start: a wave refills here once all 64 lanes are idle (the crop's tiles are whole, a queue chunk is one tile).
+        lb.iqpt_debug_set_resident_refill.argtypes = [C.c_void_p, C.c_uint32]
+        _lib.check(lb.iqpt_debug_set_resident_refill(pt._h, 64), "iqpt_debug_set_resident_refill")
     opts = []
     for s in launches:
         pt.render(s)

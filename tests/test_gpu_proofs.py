@@ -14,6 +14,8 @@ sphere behind the camera, triangles straddling t_min, at t ~ 999.99, edge-on, co
 five cameras (the default, pitched and yawed, 5 and 120 degree fields of view, 1e4 units from the origin), three
 frames (40 x 24, a ragged 37 x 19, a ragged row share with ystep 2), depths 2 and 8. One context and one oracle
 frame serve a case's ten scenes (two seeds per camera), so the masks are rebuilt for each and the pixel state runs on.
+Every case runs twice: on the five cameras and on the aligned form of each (iqpt_camera_align), with
+scenes of their own and the same coverage asked of both.
 
 The coverage each family must produce is asserted from the read-back masks over a case's scenes together."""
 import ctypes as C
@@ -24,7 +26,7 @@ import pytest
 import oracle
 from helpers import compare
 from iqpt import PathTracer, _lib, pixel_set
-from proof_masks import cameras, check_masks, random_scene, read_proofs
+from proof_masks import N_PLAIN, cameras, check_masks, random_scene, read_proofs
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +39,11 @@ FRAMES = {
 }
 LAUNCHES = [1, 3]
 REPS = 2                     # scenes per camera and case: 10 scenes share a context
+GROUPS = (0, 1)              # proof_masks.cameras: the five cameras, their aligned forms
 
 
-def seed_of(family, frame, k, rep=0):
-    return 1000 * FAMILIES.index(family) + 100 * list(FRAMES).index(frame) + 10 * rep + k
+def seed_of(family, frame, k, rep=0, group=0):
+    return 1000 * FAMILIES.index(family) + 100 * list(FRAMES).index(frame) + 10 * rep + k + N_PLAIN * group
 
 
 def last_options(pt):
@@ -60,7 +63,7 @@ def pixel_mask_info(pt):
     return n.value, bool(every.value)
 
 
-def run_case(family, frame, mode=2):
+def run_case(family, frame, mode=2, group=0):
     w, h, psargs, depth = FRAMES[frame]
     ps = pixel_set(w, h, *psargs) if psargs else pixel_set(w, h)
     mats = family == "materials"
@@ -70,8 +73,9 @@ def run_case(family, frame, mode=2):
     _lib.check(lb.iqpt_debug_set_pixel_masks(pt._h, mode), "iqpt_debug_set_pixel_masks")
     fr = oracle.OracleFrame(w, h, pixels=ps, max_depth=depth)
     tot = dict(hit=0, miss=0, mixed_tiles=0, cleared_tiles=0, pm_tiles=0, anyhit=0, certain_scenes=0, list_scenes=0)
-    for rep, (k, (cname, cam)) in ((r, kc) for r in range(REPS) for kc in enumerate(cameras(w, h))):
-        sc = random_scene(family, seed_of(family, frame, k, rep), k, cam, ps)
+    cams = cameras(w, h)[N_PLAIN * group:N_PLAIN * (group + 1)]
+    for rep, (k, (cname, cam)) in ((r, kc) for r in range(REPS) for kc in enumerate(cams)):
+        sc = random_scene(family, seed_of(family, frame, k, rep, group), k, cam, ps)
         pk = sc.build_packet()
         pt.set_camera(cam)
         pt.upload_packet(pk)
@@ -108,9 +112,10 @@ def run_case(family, frame, mode=2):
 def test_resident_scenes(require_gpu, frame):
     """Tens of random triangles and a few spheres under the reference's materials: the certain-hit fold, the sky
     kernel and the tile masks together."""
-    tot = run_case("resident", frame)
-    assert tot["certain_scenes"] == 5 * REPS
-    assert tot["hit"] > 20 and tot["miss"] > 20 and tot["mixed_tiles"] > 5, tot
+    for group in GROUPS:
+        tot = run_case("resident", frame, group=group)
+        assert tot["certain_scenes"] == 5 * REPS
+        assert tot["hit"] > 20 and tot["miss"] > 20 and tot["mixed_tiles"] > 5, tot
 
 
 @pytest.mark.parametrize("mode", [2, 1])
@@ -120,22 +125,25 @@ def test_triangle_only_scenes(require_gpu, frame, mode):
     mode 2 for the streamed scenes (two balls), iqpt_anyhit_kernel. The one-ball scenes are resident and have certain
     masks as well; in frames of 5 x 3 tiles nearly every tile keeps more than the 96 candidate pairs the certain
     proofs take, so those masks are compared but no count of certain pixels is asked of this family."""
-    tot = run_case("tris", frame, mode)
-    assert tot["list_scenes"] == 5 * REPS and tot["certain_scenes"] == 3 * REPS
-    assert tot["pm_tiles"] > 20 and tot["cleared_tiles"] > 20, tot
-    assert (tot["anyhit"] > 0) == (mode == 2), tot
+    for group in GROUPS:
+        tot = run_case("tris", frame, mode, group=group)
+        assert tot["list_scenes"] == 5 * REPS and tot["certain_scenes"] == 3 * REPS
+        assert tot["pm_tiles"] > 20 and tot["cleared_tiles"] > 20, tot
+        assert (tot["anyhit"] > 0) == (mode == 2), tot
 
 
 @pytest.mark.parametrize("frame", list(FRAMES))
 def test_triangle_and_sphere_scenes(require_gpu, frame):
     """More than 512 triangles plus spheres: the plain kernel walks the lists through the per-pixel masks."""
-    tot = run_case("tris_spheres", frame)
-    assert tot["list_scenes"] == 5 * REPS and tot["anyhit"] == 0
-    assert tot["pm_tiles"] > 20 and tot["cleared_tiles"] > 20, tot
+    for group in GROUPS:
+        tot = run_case("tris_spheres", frame, group=group)
+        assert tot["list_scenes"] == 5 * REPS and tot["anyhit"] == 0
+        assert tot["pm_tiles"] > 20 and tot["cleared_tiles"] > 20, tot
 
 
 @pytest.mark.parametrize("frame", list(FRAMES))
 def test_scenes_with_a_material_table(require_gpu, frame):
     """A material table: no certain masks are built; the tile masks are, and the frame is still exact."""
-    tot = run_case("materials", frame)
-    assert tot["certain_scenes"] == 0 and tot["hit"] == 0 and tot["miss"] == 0
+    for group in GROUPS:
+        tot = run_case("materials", frame, group=group)
+        assert tot["certain_scenes"] == 0 and tot["hit"] == 0 and tot["miss"] == 0

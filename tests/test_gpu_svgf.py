@@ -15,7 +15,7 @@ import iqpt
 import oracle
 import svgf_ref as sr
 import temporal_ref as tr
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Svgf, Temporal, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Svgf, Temporal, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 NO = sr.NO_PRIM
@@ -192,7 +192,7 @@ def beside(sc, with_svgf):
         r.upload_scene(sc)
         for k in range(3):
             cam = view_camera(k)
-            pt.set_camera(cam)
+            pt.set_camera(align_camera(cam))              # DESIGN.md §9.7; every other object takes the plain one
             pt.reset()
             r.set_camera(cam)
             t.begin_view_raster(r)
@@ -229,7 +229,7 @@ def test_scenes(require_gpu, name):
         r.upload_scene(sc)
         for k in range(3):
             cam = view_camera(k)
-            pt.set_camera(cam)
+            pt.set_camera(align_camera(cam))              # DESIGN.md §9.7; every other object takes the plain one
             pt.reset()
             r.set_camera(cam)
             s.begin_view_raster(r)
@@ -255,7 +255,7 @@ def test_scenes(require_gpu, name):
                 assert np.all(np.isfinite(v)) and np.all(v >= 0)
                 spatial.append(ref.stats())
             fr.reset()
-            fr.render(pk, cam, 2)
+            fr.render(pk, align_camera(cam), 2)
         # the first view is all spatial; later ones take the temporal estimate where the history holds
         guided, valid, took = spatial[0]
         assert valid == 0 and took == guided > W * H // 4

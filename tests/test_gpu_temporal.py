@@ -11,7 +11,7 @@ import denoise_ref as dr
 import iqpt
 import oracle
 import temporal_ref as tr
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Temporal, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Temporal, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 NO = tr.NO_PRIM
@@ -191,7 +191,7 @@ def test_scenes(require_gpu, name):
         r.upload_scene(sc)
         for k in range(3):
             cam = view_camera(k)
-            pt.set_camera(cam)
+            pt.set_camera(align_camera(cam))              # DESIGN.md §9.7; every other object takes the plain one
             pt.reset()
             r.set_camera(cam)
             t.begin_view_raster(r)
@@ -215,7 +215,7 @@ def test_scenes(require_gpu, name):
                 assert_same(t.read(), want, f"{name} view {k} spp {spp}")
                 assert_same(t_host.read(), want, f"{name} view {k} spp {spp} (host planes)")
             fr.reset()
-            fr.render(pk, cam, 2)
+            fr.render(pk, align_camera(cam), 2)
         assert float(want[0][ids != NO][:, 3].mean()) > 4.0          # 2 + 2 + 2 samples where the history held
         # the path tracer is untouched: accumulator, frame and RNG states still equal the oracle's
         acc, acc_bgra = pt.read()
@@ -237,7 +237,7 @@ def test_denoise_chain_clear_and_copies(require_gpu):
         out_ptr = t.output_device()
         for k in range(2):
             cam = view_camera(k)
-            pt.set_camera(cam)
+            pt.set_camera(align_camera(cam))              # DESIGN.md §9.7; every other object takes the plain one
             pt.reset()
             pt.render(1)
             r.set_camera(cam)

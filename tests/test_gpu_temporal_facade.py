@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Temporal, _build, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Temporal, _build, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +30,7 @@ def sequence(preset, w, h, depth, views, params, denoise=None):
         pt.upload_packet(sc.build_packet())
         r.upload_scene(sc)
         for cam, launches, spp in views:
-            pt.set_camera(cam)
+            pt.set_camera(align_camera(cam))              # what the renderer and the CLI give it
             pt.reset()
             r.set_camera(cam)
             t.begin_view_raster(r)

@@ -13,7 +13,7 @@ import denoise_ref as dr
 import iqpt
 import oracle
 import upscale_ref as ur
-from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Upscaler, make_camera
+from iqpt import Denoiser, PathTracer, Rasterizer, Scene, Upscaler, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 NO = ur.NO_PRIM
@@ -191,7 +191,7 @@ def test_frame_end_to_end(require_gpu):
     cam_hi, cam_lo = make_camera(W, H), make_camera(w, h)
     with PathTracer(w, h, max_depth=depth) as pt, Rasterizer(w, h) as r_lo, Rasterizer(W, H) as r_hi, \
             Upscaler(W, H, F) as u, Denoiser(W, H) as d:
-        pt.set_camera(cam_lo)
+        pt.set_camera(align_camera(cam_lo))               # DESIGN.md §9.7; the two rasterizers take the plain ones
         pt.upload_packet(pk)
         pt.render(spp)
         for r, cam in ((r_lo, cam_lo), (r_hi, cam_hi)):
@@ -209,7 +209,7 @@ def test_frame_end_to_end(require_gpu):
         assert u.stats() == counts and sum(counts) == W * H and counts[0] > 0.98 * W * H
         # the lo path tracer is untouched: accumulator, frame and RNG states still equal the oracle's
         fr = oracle.OracleFrame(w, h, max_depth=depth)
-        fr.render(pk, cam_lo, spp)
+        fr.render(pk, align_camera(cam_lo), spp)
         assert np.array_equal(bits(acc), bits(fr.lin)) and np.array_equal(acc_bgra, fr.bgra)
         assert np.array_equal(pt.read_rng(), fr.states)
         # the same call again gives the same bits

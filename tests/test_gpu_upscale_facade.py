@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import upscale_ref as ur
-from iqpt import PathTracer, Rasterizer, Scene, _build, make_camera
+from iqpt import PathTracer, Rasterizer, Scene, _build, align_camera, make_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +26,7 @@ def reference_frames(preset, W, H, f, launches, spp, depth):
     sc = Scene()
     sc.add_preset(preset)
     with PathTracer(w, h, max_depth=depth) as pt, Rasterizer(w, h) as r_lo, Rasterizer(W, H) as r_hi:
-        pt.set_camera(make_camera(w, h))
+        pt.set_camera(align_camera(make_camera(w, h)))    # what the facade test and the CLI give it
         pt.upload_packet(sc.build_packet())
         for _ in range(launches):
             pt.render(spp)

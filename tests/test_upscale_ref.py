@@ -265,3 +265,18 @@ def test_quality_and_classes_on_the_oracle_frames():
     assert sum(counts) == W * H
     assert shares[2] <= 0.01 and shares[1] <= 0.02
     assert r <= (1 + R_MEASURED) / 2
+
+
+# the edge figure under the two camera pairings, measured with tests/edge_quality.py
+EDGE_ONE_CAMERA, EDGE_ALIGNED = 0.14070, 0.12010
+
+
+def test_edge_quality_with_the_aligned_cameras():
+    """The frames of the test above with the lo path tracer under the aligned lo camera and the truth under the
+    aligned hi camera, RMSE of the upsampled 16-spp frame over the hi pixels within one pixel of an id edge (14.5 % of
+    the frame): at most the midpoint of the two measured figures. Over the whole frame 0.0690 becomes 0.0542."""
+    import edge_quality as eq
+    from iqpt import align_camera
+    fig = eq.upscale_figures(align_camera)
+    print(eq.show("upscale, aligned", fig))
+    assert fig["out_edge"] <= (EDGE_ONE_CAMERA + EDGE_ALIGNED) / 2

@@ -44,7 +44,9 @@ extern "C" {
 #endif
 
 /* 6 (round 6): IQPT_SPLIT_CHAIN and IQPT_SPLIT_FAN are refused with IQPT_ERR_UNSUPPORTED (their kernels were
- * archived); the other entry points are unchanged from 5. */
+ * archived); the other entry points are unchanged from 5.
+ * The library's iqpt_debug_* exports (tests and tools) are not declared here. Among them iqpt_debug_set_limits
+ * keeps its four arguments and ignores iter_limit (the archived chain kernel's loop bound). */
 #define IQPT_ABI_VERSION 6
 
 typedef enum iqpt_status {

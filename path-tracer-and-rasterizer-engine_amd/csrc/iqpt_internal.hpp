@@ -1,4 +1,4 @@
-// iqpt_internal.hpp — types shared by the runtime (iqpt_runtime.cpp) and the kernels
+// iqpt_internal.hpp — types shared by the runtime (iqpt_runtime.cpp, runtime/) and the kernels
 // (iqpt_kernels.hip), plus the error plumbing of the C ABI.
 #pragma once
 
@@ -174,7 +174,7 @@ struct kparams {
     uint32_t* ovl_err;               // bit 0: a wait exceeded spin_limit, bit 2: an XCD's tile list was never taken
                                      // (no workgroup ran there)
     // forward-progress bound (never reached by a real launch; iqpt_debug_set_limits lowers it so that tests can
-    // force it): s_sleep polls of one per-tile wait; iter_limit bounded the archived chain kernel's loop (unused)
+    // force it): s_sleep polls of one per-tile wait; iter_limit bounded the archived chain kernel's loop (unused, 0)
     uint32_t spin_limit, iter_limit;
     // iqpt_fan_kernel: the lanes of fan tile b that it renders (bit i: pixel i of the tile); null = all.
     // Spec launches give the fan kernel every pixel whose camera rays provably miss every sphere, also
@@ -195,7 +195,6 @@ constexpr uint32_t kRaySlots = 64;
 constexpr uint32_t kRaySlotStride = 16;      // unsigned long longs
 constexpr int kSphNodeFloat4 = 3;
 constexpr uint32_t kOverlapSpinLimit = 1u << 23;   // s_sleep(20) polls before a wait gives up (~seconds)
-constexpr uint32_t kChainIterLimit = 1u << 22;     // (the archived chain kernel's loop bound; iqpt_debug_set_limits)
 // two launch parities x (8 XCD queue words + the finished-block count), 64 B apart
 constexpr uint32_t kOverlapQueueWords = 2 * 9 * 16;
 
@@ -277,6 +276,13 @@ struct ksplit {
 constexpr uint32_t kSplitMCapMul = 3;    // window cap M <= 3 spp (rounded up to 16)
 constexpr uint32_t kSplitRunLen = 8;     // R: slots per speculative run
 constexpr uint32_t kSplitHeavyRho = 320; // heavy pixel: >= 1.25 slots per sample last launch (x 256)
+// the window cap of a launch of spp samples (split slots, spec windows): kSplitMCapMul spp, rounded up to 16
+__host__ __device__ inline uint32_t split_m_cap(uint32_t spp) { return (kSplitMCapMul * spp + 15u) & ~15u; }
+// LDS bytes of the running-mean table of a launch of spp samples: spp float2 (padded to 16 B), then spp floats
+// (likewise)
+__host__ __device__ inline uint32_t acc_table_lds_bytes(uint32_t spp) {
+    return ((spp + 1u) & ~1u) * 8u + ((spp + 3u) & ~3u) * 4u;
+}
 
 // The window of a split pixel for a launch of spp samples: its last chain's slots per sample rho
 // (x 256) times spp, plus a margin of an eighth of the extra slots (at least 2), + 2; 1.5 spp without
@@ -457,8 +463,6 @@ int launch_fan(void* stream, const kparams& p, uint32_t ntiles, int opt);
 // kernel this thread launches (hipExtLaunchKernel) rather than by marker packets of their own; a launch
 // function that launches nothing leaves them bound — the caller unbinds (nullptr, nullptr).
 void bind_launch_events(void* start, void* stop);
-// the events bound to the next launch (and unbind them): a launch of several kernels binds them to its first and last
-void take_launch_events(void** start, void** stop);
 constexpr int kRenderBlock = 256;
 constexpr uint32_t kQueueChunk = 64;
 const char* render_kernel_name();

@@ -3371,7 +3371,7 @@ __device__ __forceinline__ uint32_t fan_range(uint32_t cn, uint32_t w) {
 }
 
 __host__ __device__ inline uint32_t fan_lds_bytes(uint32_t ntri_pairs, uint32_t spp) {
-    return ntri_pairs * kTriPairFloat4 * 16u + ((spp + 1u) & ~1u) * 8u + ((spp + 3u) & ~3u) * 4u + 16u * 4u +
+    return ntri_pairs * kTriPairFloat4 * 16u + acc_table_lds_bytes(spp) + 16u * 4u +
            kFanChunk * 64u * 4u + kFanChunk * 8u;
 }
 
@@ -4270,7 +4270,7 @@ const variant kVariants[] = {
     // scenes with LDS batches run without the 5-wave bound (4 waves/SIMD); the batch-free BVH-primary
     // variants keep it (5 waves measured 2.5 % faster on C5 than 4, 6 slower: profiles/ab/r01_ab72).
     // Streamed scenes also get the kOptBvhPrimary form (camera rays through the BVH), chosen per
-    // packet by timing (iqpt_runtime.cpp).
+    // packet by timing (runtime/iq_launch.cpp).
     // Resident variants carry kOptPrio (waves holding scatter-heavy tiles win VALU arbitration: the
     // launch ends with the longest chains, profiles/r02/ab_prio.json); the runtime adds the bit.
 #define IQPT_PROD(O) IQPT_V(8, false, (O) | kOptPrio), IQPT_V(16, false, (O) | kOptPrio), IQPT_V(8, true, (O) & ~kOptLB5), \
@@ -4349,12 +4349,6 @@ const variant* find_variant(int max_depth, bool stream, int opt) {
 }
 
 }  // namespace
-
-void take_launch_events(void** start, void** stop) {
-    *start = tl_ev_start;
-    *stop = tl_ev_stop;
-    tl_ev_start = tl_ev_stop = nullptr;
-}
 
 void bind_launch_events(void* start, void* stop) {
     tl_ev_start = (hipEvent_t)start;
@@ -4582,7 +4576,7 @@ int launch_sky(void* stream, const kparams& p, const uint32_t* tiles, uint32_t n
     const sky_variant* v = find_sky(opt);
     if (!v || p.spp > kAccTableMax || p.miss == nullptr || tiles == nullptr) return (int)hipErrorInvalidDeviceFunction;
     if (ntiles == 0 || p.spp == 0) return 0;
-    return v->launch((hipStream_t)stream, p, tiles, ntiles, ((p.spp + 1u) & ~1u) * 8u + ((p.spp + 3u) & ~3u) * 4u);
+    return v->launch((hipStream_t)stream, p, tiles, ntiles, acc_table_lds_bytes(p.spp));
 }
 
 // iqpt_anyhit_kernel launches: keyed like the sky kernel (camera form, division forms)
@@ -4621,7 +4615,7 @@ int launch_anyhit(void* stream, const kparams& p, int opt) {
         return (int)hipErrorInvalidDeviceFunction;
     if (p.ntiles == 0 || p.spp == 0) return 0;
     return v->launch((hipStream_t)stream, p,
-                     ((p.spp + 1u) & ~1u) * 8u + ((p.spp + 3u) & ~3u) * 4u + (kAnyBlock / 64u) * kAnyMaxEntries * 4u);
+                     acc_table_lds_bytes(p.spp) + (kAnyBlock / 64u) * kAnyMaxEntries * 4u);
 }
 
 uint32_t fan_lds(const kparams& p) { return fan_lds_bytes(p.ntri_pairs, p.spp); }

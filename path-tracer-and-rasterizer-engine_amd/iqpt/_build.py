@@ -48,6 +48,10 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", *FP_FLAGS,
              f"-I{INCLUDE}", f"-I{CSRC}"]
 
 LIB_SOURCES = ["iqpt_kernels.hip", "iqpt_runtime.cpp", "iq_scene.cpp", "path_tracer.cpp",
+               # the rest of the C ABI by concern; runtime/iq_ctx.hpp is theirs alone, outside
+               # kernel_source_sha16's identity
+               "runtime/iq_cull.cpp", "runtime/iq_launch.cpp", "runtime/iq_comm.cpp", "runtime/iq_checkpoint.cpp",
+               "runtime/iq_debug.cpp",
                # the rasterizer: its own directory, outside kernel_source_sha16's path-tracing identity
                "raster/iq_raster_kernels.hip", "raster/iq_raster.cpp", "raster/rasterizer.cpp",
                # the rasterizer-guided denoiser, likewise outside that identity
@@ -94,7 +98,7 @@ def _headers() -> list[Path]:
     return sorted(CSRC.glob("*.h")) + sorted(CSRC.glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 
 
-SUBDIRS = ("raster", "denoise", "temporal", "svgf", "post", "upscale")
+SUBDIRS = ("runtime", "raster", "denoise", "temporal", "svgf", "post", "upscale")
 
 
 def _deps() -> list[Path]:

@@ -1,5 +1,5 @@
 """kOptCamAxis (the short camera transform for pitch-only cameras, iqpt_kernels.hip camera_ray_axis):
-which cameras qualify (host check, iqpt_runtime.cpp cam_axis_constants), and the exactness argument
+which cameras qualify (host check, runtime/iq_cull.cpp cam_axis_constants), and the exactness argument
 replayed in numpy binary32 — the general chain of camera_ndc (camera.cu:20-43 as the kernel and the
 oracle evaluate it) against the short chain, bit for bit including the signs of zeros, on random
 and adversarial NDC inputs (x_ndc = +-0, tiny, large) and on cameras whose kept terms vanish."""

@@ -2,7 +2,7 @@
 """Executed work per ray of the render kernel (the roofline numerator for the BVH / culled configs).
 
 For a config (c2, c4, c5) this runs the production path of the A/B library until its camera-ray path
-choice is made (iqpt_runtime.cpp tune stages), reads the option set it settled on, then renders with the
+choice is made (runtime/iq_launch.cpp tune stages), reads the option set it settled on, then renders with the
 kOptStats build of that option set and reads the per-lane counters (iqpt_kernels.hip stat_add and the
 BVH counters): Möller–Trumbore triangle tests, sphere tests, triangle-BVH node tests and sphere-BVH node
 tests, per closest-hit query. Executed FLOPs per ray = 52 MT + 19 sphere (shape.cu:65-92,

@@ -239,6 +239,55 @@ __device__ __forceinline__ void camera_ray(const kparams& p, uint32_t x, uint32_
     else camera_ndc<OPT>(p, x_ndc, y_ndc, r);
 }
 
+// Two consecutive samples of one pixel, element 0 = sample k, element 1 = sample k + 1 (iqpt_sky_kernel's paired
+// body): camera_ray twice, with the binary32 work of both samples in packed operations. The four
+// draws first, in the reference's order (x then y jitter of sample k, then of sample k + 1); after them every
+// element goes through camera_ray's and camera_ray_axis' operations on its own operands in their order, so each
+// ray has the bits camera_ray gives it. Pitch-only cameras with the short division forms only (the production set):
+//  * (x + jx) / W and (y + jy) / H are iq_div_pre without v_div_fixup_f32: the dividend is +0 or finite with a
+//    magnitude in [2^-32, 2^24] (never -0: x + jx = 0 only as 0 + (0.5 - 0.5) = +0) and the divisor is in [1, 2^24],
+//    so the quotient is +0 or normal, and for such operands the fixup returns its first operand with the quotient's
+//    sign, which the corrected quotient already has (iq_fp2.h, iq_div_pre2_nf; +0 stays +0 through q, r and q1);
+//  * 1 / len likewise (iq_rcp2_nf): the runtime proves len in [1e-5, 2^100) for every ray of the frame
+//    (camera_ray_axis).
+// camera_ray_axis packs (near, far) of one sample; here near and far each hold both samples: 27 packed operations
+// per pair of samples where the (near, far) form takes 17 per sample.
+struct ray3x2 {
+    f2 ox, oy, oz, dx, dy, dz;
+};
+
+constexpr float kU32ToUnit = 0x1p-32f;      // iq_u32_to_unit's factor
+static_assert(kU32ToUnit == 2.3283064365386963e-10f, "iq_u32_to_unit multiplies by 2^-32");
+
+template <int OPT>
+__device__ __forceinline__ void camera_ray_pair(const kparams& p, uint32_t x, uint32_t y, rng6& s, ray3x2& r) {
+    static_assert((OPT & kOptCamAxis) && (OPT & kOptFastDiv), "camera_ray_pair: pitch-only cameras, short divisions");
+    const uint32_t ux0 = xorwow_next(s), uy0 = xorwow_next(s), ux1 = xorwow_next(s), uy1 = xorwow_next(s);
+    // rand_real(s, -0.5f, 0.5f): u * (hi - lo) + lo
+    const f2 jx = ((f2){(float)ux0, (float)ux1} * kU32ToUnit) * (0.5f - -0.5f) + -0.5f;
+    const f2 jy = ((f2){(float)uy0, (float)uy1} * kU32ToUnit) * (0.5f - -0.5f) + -0.5f;
+    const float wf = (float)p.width, hf = (float)p.height;
+    const f2 xs = (float)x + jx, ys = (float)y + jy;
+    const f2 x_ndc = iq_div_pre2_nf(xs, (f2){wf, wf}, (f2){p.rcp_width, p.rcp_width}) * 2.0f - 1.0f;
+    const f2 y_ndc = 1.0f - iq_div_pre2_nf(ys, (f2){hf, hf}, (f2){p.rcp_height, p.rcp_height}) * 2.0f;
+    // camera_ray_axis, its (near, far) pairs spelled as near and far
+    const float* k = p.cam_ax;
+    const f2 xc = x_ndc * k[0] + k[2], yc = y_ndc * k[1] + k[3];
+    const f2 xn = xc * k[4], xf = xc * k[5], yn = yc * k[4], yf = yc * k[5];
+    const f2 wxn = xn * k[6] + k[7], wxf = xf * k[6] + k[7];
+    const f2 wyn = (yn * k[8] + k[12]) + k[10], wyf = (yf * k[8] + k[13]) + k[10];
+    const f2 wzn = (yn * k[9] + k[14]) + k[11], wzf = (yf * k[9] + k[15]) + k[11];
+    const f2 dx = wxf - wxn, dy = wyf - wyn, dz = wzf - wzn;
+    const f2 len = iq_sqrt_n2((dx * dx + dy * dy) + dz * dz);
+    const f2 inv = iq_rcp2_nf(len);
+    r.ox = wxn;
+    r.oy = wyn;
+    r.oz = wzn;
+    r.dx = dx * inv;
+    r.dy = dy * inv;
+    r.dz = dz * inv;
+}
+
 // n XORWOW steps of the xorshift part (random.cu:66-107; the Weyl word d is the caller's, d += n WEYL).
 // Five steps at a time: each new word takes the slot of the word it retires (x_{k+5} = f(x_k, x_{k+4})),
 // so after five steps v0..v4 name the state again and no register moves are needed; the rest one by one.
@@ -668,6 +717,38 @@ __device__ __forceinline__ void mean_terms(float cx, float cy, float cz, float n
     qx = cx == 1.0f ? rc : (cx == 0.0f ? 0.0f : cx / nf);
     qy = cy == 1.0f ? rc : (cy == 0.0f ? 0.0f : cy / nf);
     qz = cz == 1.0f ? rc : (cz == 0.0f ? 0.0f : cz / nf);
+}
+
+// The sky gradient of a miss (path_tracer.cu:308-313): (1 - a) white + a (0.5, 0.7, 1) with a = (dir.y + 1) / 2, one
+// spelling for every kernel. T is float, or f2 for two samples of a pixel (iqpt_sky_kernel's paired body): a
+// packed operation rounds each element like the scalar one. The expression is written once, in sky_gradient_of(a);
+// the plain and spec kernels take the colour by value and the fan, sky and any-hit kernels, which clamp it next, through
+// references: with these two shapes every kernel's instructions are those of the spelled-out form (compared kernel by
+// kernel), while either shape alone moved the register allocation of the kernels that use the other.
+template <typename T>
+struct sky_rgb {
+    T x, y, z;
+};
+template <typename T>
+__device__ __forceinline__ sky_rgb<T> sky_gradient_of(T a) {
+    const T one_a = 1.0f - a;
+    return {one_a + a * 0.5f, one_a + a * 0.7f, one_a + a * 1.0f};
+}
+template <typename T>
+__device__ __forceinline__ T sky_gradient_param(T dy) {
+    return (dy + 1.0f) * 0.5f;
+}
+template <typename T>
+__device__ __forceinline__ sky_rgb<T> sky_gradient(T dy) {
+    return sky_gradient_of(sky_gradient_param(dy));
+}
+// ... and into the caller's three channels, for the kernels that clamp them next
+template <typename T>
+__device__ __forceinline__ void sky_gradient_of(T a, T& cx, T& cy, T& cz) {
+    const sky_rgb<T> g = sky_gradient_of(a);
+    cx = g.x;
+    cy = g.y;
+    cz = g.z;
 }
 
 // Closest hit over the primitives in [tri0, tri1) / [sph0, sph1) of the given base arrays (LDS),
@@ -1856,11 +1937,10 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
             bool need_a = false;
             // the sky gradient of a miss, :308-313
             auto sky = [&](float& Lx, float& Ly, float& Lz) {
-                const float a = (ray.dy + 1.0f) * 0.5f;
-                const float one_a = 1.0f - a;
-                Lx = one_a + a * 0.5f;
-                Ly = one_a + a * 0.7f;
-                Lz = one_a + a * 1.0f;
+                const sky_rgb<float> g = sky_gradient(ray.dy);
+                Lx = g.x;
+                Ly = g.y;
+                Lz = g.z;
             };
             // a path's end: backward product (:321-324), clamp (:345-347), path_color = 0 + color, running mean
             // (:356-358). True when the pixel's samples of this launch are done.
@@ -2374,11 +2454,10 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                     }
                 } else {
                     term = true;                     // sky gradient, :308-313
-                    const float a = (ray.dy + 1.0f) * 0.5f;
-                    const float one_a = 1.0f - a;
-                    Lx = one_a + a * 0.5f;
-                    Ly = one_a + a * 0.7f;
-                    Lz = one_a + a * 1.0f;
+                    const sky_rgb<float> g = sky_gradient(ray.dy);
+                    Lx = g.x;
+                    Ly = g.y;
+                    Lz = g.z;
                 }
             } else if (active) {
                 if (kind == kHitSphere) {
@@ -2411,11 +2490,10 @@ __global__ __launch_bounds__(kRenderBlock, (min_waves_per_simd<OPT, STREAM>())) 
                     Lz = 10.0f;
                 } else {
                     term = true;                     // sky gradient, :308-313
-                    const float a = (ray.dy + 1.0f) * 0.5f;
-                    const float one_a = 1.0f - a;
-                    Lx = one_a + a * 0.5f;
-                    Ly = one_a + a * 0.7f;
-                    Lz = one_a + a * 1.0f;
+                    const sky_rgb<float> g = sky_gradient(ray.dy);
+                    Lx = g.x;
+                    Ly = g.y;
+                    Lz = g.z;
                 }
             }
             if (OPT & kOptStats) {
@@ -3486,7 +3564,7 @@ __device__ __forceinline__ void fan_body(const kparams& p, uint32_t bid) {
             }
             const uint64_t hit = __ballot(kind == kHitTri);
             if (lane == 0) lds_hit[s - c0] = hit;
-            lds_sky[(s - c0) * 64u + lane] = (ray.dy + 1.0f) * 0.5f;   // sky gradient parameter (:308-313)
+            lds_sky[(s - c0) * 64u + lane] = sky_gradient_param(ray.dy);   // sky gradient parameter (:308-313)
         }
         pos = s1;
         __syncthreads();
@@ -3501,11 +3579,8 @@ __device__ __forceinline__ void fan_body(const kparams& p, uint32_t bid) {
                     qy = tv.x;
                     qz = tv.x;
                 } else {
-                    const float a = lds_sky[k * 64u + lane];
-                    const float one_a = 1.0f - a;
-                    float cx = one_a + a * 0.5f;
-                    float cy = one_a + a * 0.7f;
-                    float cz = one_a + a * 1.0f;
+                    float cx, cy, cz;
+                    sky_gradient_of(lds_sky[k * 64u + lane], cx, cy, cz);
                     cx = cx > 1.0f ? 1.0f : (cx < 0.0f ? 0.0f : cx);
                     cy = cy > 1.0f ? 1.0f : (cy < 0.0f ? 0.0f : cy);
                     cz = cz > 1.0f ? 1.0f : (cz < 0.0f ? 0.0f : cz);
@@ -3805,11 +3880,10 @@ __device__ __forceinline__ void spec_body(const kparams& p, const kspec& s, uint
                         Lz = 10.0f;
                     } else {
                         term = true;                     // sky gradient, :308-313
-                        const float a = (ray.dy + 1.0f) * 0.5f;
-                        const float one_a = 1.0f - a;
-                        Lx = one_a + a * 0.5f;
-                        Ly = one_a + a * 0.7f;
-                        Lz = one_a + a * 1.0f;
+                        const sky_rgb<float> g = sky_gradient(ray.dy);
+                        Lx = g.x;
+                        Ly = g.y;
+                        Lz = g.z;
                     }
                     if (term) {
                         // backward product (:321-324), clamp (:345-347), 0 + colour (:341, 348)
@@ -4006,6 +4080,12 @@ __device__ __forceinline__ void spec_body(const kparams& p, const kspec& s, uint
 // one tile per block: the blocks slot into the CUs beside the plain kernel's waves one wave at a time (C2 N = 1:
 // 0.840 -> 0.812 ms per step against four tiles per block, r06 run 47)
 constexpr uint32_t kSkyBlock = 64;
+// IQPT_SKY_PAIRS=0: one sample per loop trip in every variant (the form before the paired body; the A/B library of
+// iqpt/_build.py SKY_SINGLE_FLAGS)
+#ifndef IQPT_SKY_PAIRS
+#define IQPT_SKY_PAIRS 1
+#endif
+constexpr bool kSkyPairs = IQPT_SKY_PAIRS != 0;
 
 template <int OPT>
 __global__ __launch_bounds__(kSkyBlock) void iqpt_sky_kernel(const kparams p, const uint32_t* __restrict__ tiles,
@@ -4035,13 +4115,52 @@ __global__ __launch_bounds__(kSkyBlock) void iqpt_sky_kernel(const kparams p, co
                    p.rng[3 * (size_t)p.npix + pix], p.rng[4 * (size_t)p.npix + pix], p.rng[5 * (size_t)p.npix + pix]};
         const float4 a0 = reinterpret_cast<const float4*>(p.lin)[pix];
         float ax = a0.x, ay = a0.y, az = a0.z;
-        for (uint32_t k = 0; k < p.spp; ++k) {
+        uint32_t k = 0;
+        // Two samples per trip (kSkyPairs): the draws of both, then the binary32 work of both as
+        // f2 {sample k, sample k + 1}, then the two running-mean updates in order. What the one-sample body below does
+        // per sample and this path does not need:
+        //  * the two-sided clamp and 0 + c. Under kOptCamAxis the runtime proves every direction of the frame finite
+        //    with a length in [1e-5, 2^100), so dir.y is finite and |dir.y| <= 1.5 by a wide margin (a normalised
+        //    component is within a few ulp of [-1, 1]); then a is in [-0.25, 1.25] and each channel
+        //    (1 - a) + a w, w in {0.5, 0.7, 1}, is within rounding of 1 - a (1 - w), at least 1 - 1.25 * 0.5 = 0.375
+        //    and at most 1 + 0.25 * 0.5 = 1.125. Not NaN and above 0, so c < 0 never holds and 0 + c = c (no -0):
+        //    the clamp is min(c, 1);
+        //  * mean_terms' test for a channel in (0, mean_tiny): every channel is >= 0.375, so (bits(c) - 1) < (bits(tiny)
+        //    - 1) can hold only if bits(tiny) > bits(0.375). That is decided here once per launch from the kernel
+        //    argument (wave-uniform; a negative or NaN threshold has larger bits and takes the loop below too).
+        // An odd spp ends with one trip of the loop below; spp = 1 runs only that.
+        constexpr bool kPairs = kSkyPairs && (OPT & kOptCamAxis) && (OPT & kOptFastDiv) && (OPT & kOptAccTable);
+        if constexpr (kPairs) {
+            const bool lean = __float_as_uint(p.mean_tiny) <= __float_as_uint(0.375f);
+            if (lean) for (; k + 1u < p.spp; k += 2u) {
+                ray3x2 ray;
+                camera_ray_pair<OPT>(p, px, py, st, ray);
+                const sky_rgb<f2> g = sky_gradient(ray.dy);
+                const f2 cx = {__builtin_fminf(g.x.x, 1.0f), __builtin_fminf(g.x.y, 1.0f)};
+                const f2 cy = {__builtin_fminf(g.y.x, 1.0f), __builtin_fminf(g.y.y, 1.0f)};
+                const f2 cz = {__builtin_fminf(g.z.x, 1.0f), __builtin_fminf(g.z.y, 1.0f)};
+                // mean_terms' quotient (Markstein's correction of c RN(1 / n)) per channel for both samples
+                const float2 t0 = tab[k], t1 = tab[k + 1u];
+                const f2 rc = {t0.x, t1.x}, nf = {tab_n[k], tab_n[k + 1u]};
+                const f2 x0 = cx * rc, y0 = cy * rc, z0 = cz * rc;
+                const f2 qx = __builtin_elementwise_fma(__builtin_elementwise_fma(-nf, x0, cx), rc, x0);
+                const f2 qy = __builtin_elementwise_fma(__builtin_elementwise_fma(-nf, y0, cy), rc, y0);
+                const f2 qz = __builtin_elementwise_fma(__builtin_elementwise_fma(-nf, z0, cz), rc, z0);
+                // running mean (:356-358), sample k before sample k + 1
+                ax = qx.x + ax * t0.y;
+                ay = qy.x + ay * t0.y;
+                az = qz.x + az * t0.y;
+                ax = qx.y + ax * t1.y;
+                ay = qy.y + ay * t1.y;
+                az = qz.y + az * t1.y;
+            }
+        }
+        for (; k < p.spp; ++k) {
             ray3 ray;
             camera_ray<OPT>(p, px, py, st, ray);
             // sky gradient (:308-313), no records: the colour itself, clamped (:345-347), 0 + colour (:341, 348)
-            const float a = (ray.dy + 1.0f) * 0.5f;
-            const float one_a = 1.0f - a;
-            float cx = one_a + a * 0.5f, cy = one_a + a * 0.7f, cz = one_a + a * 1.0f;
+            float cx, cy, cz;
+            sky_gradient_of(sky_gradient_param(ray.dy), cx, cy, cz);
             cx = cx > 1.0f ? 1.0f : (cx < 0.0f ? 0.0f : cx);
             cy = cy > 1.0f ? 1.0f : (cy < 0.0f ? 0.0f : cy);
             cz = cz > 1.0f ? 1.0f : (cz < 0.0f ? 0.0f : cz);
@@ -4186,11 +4305,7 @@ __global__ __launch_bounds__(kAnyBlock) void iqpt_anyhit_kernel(const kparams p)
                     cy = 1.0f;
                     cz = 1.0f;
                 } else {
-                    const float a = (rs[r].dy + 1.0f) * 0.5f;    // sky gradient (:308-313)
-                    const float one_a = 1.0f - a;
-                    cx = one_a + a * 0.5f;
-                    cy = one_a + a * 0.7f;
-                    cz = one_a + a * 1.0f;
+                    sky_gradient_of(sky_gradient_param(rs[r].dy), cx, cy, cz);   // sky gradient (:308-313)
                     cx = cx > 1.0f ? 1.0f : (cx < 0.0f ? 0.0f : cx);
                     cy = cy > 1.0f ? 1.0f : (cy < 0.0f ? 0.0f : cy);
                     cz = cz > 1.0f ? 1.0f : (cz < 0.0f ? 0.0f : cz);

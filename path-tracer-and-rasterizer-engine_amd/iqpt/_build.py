@@ -241,6 +241,17 @@ def build_scatter_libs(force: bool = False) -> list[Path]:
     return [build_lib(force, flags=SCATTER_FULL_FLAGS, target=SCATTER_FULL_LIB)]
 
 
+# The sky kernel with one sample per loop trip in every variant (the form before the paired body):
+# an A/B library for bench.py --lib and the tools' --lib, and the other side of tests/test_gpu_sky_pairs.py.
+SKY_SINGLE_FLAGS = ("-DIQPT_SKY_PAIRS=0",)
+SKY_SINGLE_LIB = PKG_DIR / "libiqpt_skysingle.so"
+
+
+def build_sky_libs(force: bool = False) -> list[Path]:
+    """The library tests/test_gpu_sky_pairs.py compares the default one with (measurement and test only)."""
+    return [build_lib(force, flags=SKY_SINGLE_FLAGS, target=SKY_SINGLE_LIB)]
+
+
 def kernel_resources(target: Path = LIB_PATH, stats: bool = False) -> dict[str, dict[str, int]]:
     """Per kernel of iqpt_kernels.hip as compiled into `target` (a library build_lib has built): the compiler's
     resource remarks (-Rpass-analysis=kernel-resource-usage, kept beside the object), as
@@ -281,8 +292,8 @@ def build_all(force: bool = False) -> None:
     build_tools(force)
     build_oracle(force)
     build_ref(force)
-    with ThreadPoolExecutor(max_workers=2) as ex:
-        list(ex.map(lambda f: f(force), (build_pair_body_libs, build_scatter_libs)))
+    with ThreadPoolExecutor(max_workers=3) as ex:
+        list(ex.map(lambda f: f(force), (build_pair_body_libs, build_scatter_libs, build_sky_libs)))
 
 
 if __name__ == "__main__":

@@ -37,6 +37,9 @@ DENOISE_FACADE_TEST_PATH = PKG_DIR / "test_denoise_facade"
 TEMPORAL_FACADE_TEST_PATH = PKG_DIR / "test_temporal_facade"
 SVGF_FACADE_TEST_PATH = PKG_DIR / "test_svgf_facade"
 UPSCALE_FACADE_TEST_PATH = PKG_DIR / "test_upscale_facade"
+MOTION_LIB_PATH = PKG_DIR / "libiqpt_motion.so"              # moving-model reprojection: links libiqpt.so
+MOTION_UNIFORM_LIB_PATH = PKG_DIR / "libiqpt_motion_uniform.so"  # its wave-uniform-entry form (A/B and test only)
+MOTION_FACADE_TEST_PATH = PKG_DIR / "test_motion_facade"
 
 ARCH = os.environ.get("IQPT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
@@ -150,11 +153,68 @@ def build_lib(force: bool = False, stats: bool = False, flags: tuple[str, ...] =
     return target
 
 
+# Moving-model reprojection: a library of its own over libiqpt.so's exports, so that library's
+# dynamic symbol table stays what tests/golden/libiqpt_exports.txt pins.
+MOTION_LIB_SOURCES = ["motion/iq_motion_kernels.hip", "motion/iq_motion.cpp"]
+MOTION_KERNELS_SOURCE = "iq_motion_kernels.hip"
+MOTION_UNIFORM_FLAGS = ("-DIQM_UNIFORM_ENTRY=1",)
+
+
+def _motion_deps() -> list[Path]:
+    """_deps() and the motion directory's own headers, which no source of libiqpt.so includes."""
+    return _deps() + sorted((CSRC / "motion").glob("*.hpp")) + sorted((INCLUDE / "motion").glob("*.h"))
+
+
+def motion_remarks_path(target: Path = MOTION_LIB_PATH) -> Path:
+    """The view and stats kernels' resource remarks of the motion library `target`, kept beside its objects."""
+    return BUILD_DIR / target.stem / (MOTION_KERNELS_SOURCE + ".remarks.txt")
+
+
+def build_motion_lib(force: bool = False, flags: tuple[str, ...] = (), target: Path | None = None) -> Path:
+    """libiqpt_motion.so: the main library's flags, linked against libiqpt.so in the package directory."""
+    target = target or MOTION_LIB_PATH
+    lib = build_lib(force)
+    srcs = [CSRC / s for s in MOTION_LIB_SOURCES]
+    if not force and _newer(target, srcs + _motion_deps() + [lib, Path(__file__)]):
+        return target
+    bdir = BUILD_DIR / target.stem
+    bdir.mkdir(parents=True, exist_ok=True)
+    objs = []
+    for s in srcs:
+        o = bdir / (s.name + ".o")
+        cmd = [HIPCC, *HIP_FLAGS, *flags, "-x", "hip", "-c", str(s), "-o", str(o)]
+        if s.name == MOTION_KERNELS_SOURCE:
+            _run(cmd + [REMARKS_FLAG], stderr_to=motion_remarks_path(target))
+        else:
+            _run(cmd)
+        objs.append(o)
+    tmp = target.with_suffix(".so.tmp")
+    _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", *map(str, objs), f"-L{PKG_DIR}", "-liqpt",
+          "-Wl,-rpath,$ORIGIN", "-o", str(tmp)])
+    os.replace(tmp, target)
+    return target
+
+
+def build_motion_libs(force: bool = False) -> list[Path]:
+    """The default motion library (every lane gathers its entry) and the one with wave-uniform entry loads that
+    tests/test_gpu_motion.py and tools/motion_bench.py compare it with."""
+    return [build_motion_lib(force),
+            build_motion_lib(force, flags=MOTION_UNIFORM_FLAGS, target=MOTION_UNIFORM_LIB_PATH)]
+
+
 def build_tools(force: bool = False) -> list[Path]:
     """C++ programs over the facades: the headless CLI, the path_tracer facade test, the two-engine renderer test,
-    the tests of the renderer's denoise, temporal and svgf blocks and the test of iqpt::upscaler."""
+    the tests of the renderer's denoise, temporal and svgf blocks, the test of iqpt::upscaler and, over both
+    libraries, the test of iqpt::motion."""
     lib = build_lib(force)
     out = []
+    src, dst = CSRC / "tools" / "test_motion_facade.cpp", MOTION_FACADE_TEST_PATH
+    if src.exists():
+        mlib = build_motion_lib(force)
+        if force or not _newer(dst, [src, lib, mlib] + _motion_deps()):
+            _run([HIPCC, "-O2", "-std=c++17", *FP_FLAGS, f"-I{INCLUDE}", f"-I{CSRC}", str(src),
+                  f"-L{PKG_DIR}", "-liqpt_motion", "-liqpt", "-Wl,-rpath,$ORIGIN", "-o", str(dst)])
+        out.append(dst)
     for src, dst in ((CSRC / "tools" / "iqpt_cli.cpp", CLI_PATH),
                      (CSRC / "tools" / "test_facade.cpp", FACADE_TEST_PATH),
                      (CSRC / "tools" / "test_raster_facade.cpp", RASTER_FACADE_TEST_PATH),
@@ -289,6 +349,7 @@ def build_ref(force: bool = False) -> Path | None:
 
 def build_all(force: bool = False) -> None:
     build_lib(force)
+    build_motion_libs(force)
     build_tools(force)
     build_oracle(force)
     build_ref(force)

@@ -229,6 +229,38 @@ TEMPORAL_SIGNATURES = [
 ]
 
 
+class MotionEntry(C.Structure):
+    """iqpt_motion_entry (include/motion/iqpt_motion.h): 128 bytes."""
+    _fields_ = [("back", C.c_float * 16), ("nback", C.c_float * 12), ("moved", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+MOTION_MAX_ENTRIES = 1 << 20                   # IQPT_MOTION_MAX_ENTRIES
+_MEP = C.POINTER(MotionEntry)
+# include/motion/iqpt_motion.h: moving-model reprojection, in libiqpt_motion.so (bound by load_motion, not load)
+MOTION_SIGNATURES = [
+    ("iqpt_motion_table", C.c_int, [C.POINTER(DrawItem), C.c_uint32, C.POINTER(DrawItem), C.c_uint32, _MEP]),
+    ("iqpt_motion_default_params", C.c_int, [C.POINTER(TemporalParams)]),
+    ("iqpt_motion_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    ("iqpt_motion_destroy", C.c_int, [_P]),
+    ("iqpt_motion_set_params", C.c_int, [_P, C.POINTER(TemporalParams)]),
+    ("iqpt_motion_begin_view", C.c_int, [_P, C.POINTER(Camera), _FP, C.POINTER(C.c_uint32), _P, C.c_uint32]),
+    ("iqpt_motion_begin_view_device", C.c_int, [_P, C.POINTER(Camera), _P, _P, _P, C.c_uint32]),
+    ("iqpt_motion_begin_view_raster", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("iqpt_motion_clear", C.c_int, [_P]),
+    ("iqpt_motion_resolve", C.c_int, [_P, _FP, C.c_uint64]),
+    ("iqpt_motion_resolve_device", C.c_int, [_P, _P, C.c_uint64]),
+    ("iqpt_motion_resolve_ctx", C.c_int, [_P, _P]),
+    ("iqpt_motion_read", C.c_int, [_P, _FP, C.POINTER(C.c_uint8)]),
+    ("iqpt_motion_output_device", C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    ("iqpt_motion_copy_frame_device", C.c_int, [_P, _P, C.c_size_t]),
+    ("iqpt_motion_sync", C.c_int, [_P]),
+    ("iqpt_motion_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_uint64)]),
+    ("iqpt_motion_stats", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]),
+]
+
+
 class SvgfParams(C.Structure):
     """iqpt_svgf_params (include/svgf/iqpt_svgf.h)."""
     _fields_ = [("normal_min", C.c_float), ("plane_tolerance", C.c_float), ("max_history", C.c_uint32),
@@ -324,6 +356,32 @@ def load() -> C.CDLL:
                           "rebuild with __graft_entry__.build()")
     LOADED_ABI = abi
     _lib = lib
+    return lib
+
+
+MOTION_LIB_PATH = _PKG / "libiqpt_motion.so"
+_motion_libs: dict = {}
+
+
+def load_motion(path=None) -> C.CDLL:
+    """Load libiqpt_motion.so (or another build of it, e.g. the A/B library with wave-uniform entry loads) on first use and bind
+    MOTION_SIGNATURES; libiqpt.so is loaded first, the library links it. Raises if it is absent: no fallback."""
+    load()
+    path = Path(path) if path is not None else MOTION_LIB_PATH
+    key = str(path.resolve())
+    if key in _motion_libs:
+        return _motion_libs[key]
+    if not path.exists():
+        raise ImportError(f"{path} is missing: run __graft_entry__.build() "
+                          "(the HIP extension is required; there is no CPU fallback)")
+    lib = C.CDLL(str(path))
+    for name, res, args in MOTION_SIGNATURES:
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise ImportError(f"{path} does not export {name}: rebuild with __graft_entry__.build()")
+        fn.restype = res
+        fn.argtypes = args
+    _motion_libs[key] = lib
     return lib
 
 

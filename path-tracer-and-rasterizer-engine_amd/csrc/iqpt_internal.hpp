@@ -82,9 +82,10 @@ struct kparams {
     const uint32_t* cull;
     uint32_t cull_ntx, cull_wt, cull_stride;
     // per tile, two words: the 64-bit mask of its pixels (storage order inside the tile) whose every camera
-    // ray is certain to end on an emissive triangle (no sphere candidate in the tile, a candidate triangle
-    // every ray of the pixel's bundle hits: iq_interval.h tri_certain; the reference's materials only);
-    // null = none. Such a pixel's samples are (1, 1, 1) folds and two draws each.
+    // ray is certain to end on an emissive triangle (no sphere candidate in the tile, or every sphere candidate
+    // culled for the pixel's own bundle; a candidate triangle every ray of the pixel's bundle hits:
+    // iq_interval.h tri_certain; the reference's materials only); null = none. Such a pixel's samples are
+    // (1, 1, 1) folds and two draws each. The folded plane of iqpt_certain_kernel's buffer (kCertainFolded).
     const uint32_t* certain;
     // per tile, two words: the 64-bit mask of its pixels whose every camera ray is certain to miss every
     // primitive (the pixel's own bundle culls each candidate, iq_interval.h): their samples are the sky
@@ -397,7 +398,10 @@ int launch_assemble_rows(void* stream, const uint32_t* src, uint32_t* dst, uint3
 // Tile masks for kOptCull (one thread per tile word).
 int launch_bin(void* stream, const kbin& b);
 // Per-tile candidate counts from the masks (triangle pairs, sphere pairs), and the candidate lists.
-// per tile of the masks: the certain flags of kparams::certain (one thread per tile)
+// per tile of the masks: the certain flags (one wave per tile) as kCertainPlanes planes of 2 ntiles words each —
+// the hit mask by the tile rule, the miss mask (kparams::miss), the beside-a-sphere hit mask, and the folded hit
+// mask (the first, OR the third in the tiles where enough pixels have it: kparams::certain)
+constexpr uint32_t kCertainPlanes = 4, kCertainMiss = 1, kCertainBeside = 2, kCertainFolded = 3;
 int launch_certain(void* stream, const kbin& b, uint32_t* certain);
 int launch_tile_count(void* stream, const uint32_t* cull, uint32_t ntiles, uint32_t wt, uint32_t stride,
                       uint32_t* cnt_tri, uint32_t* cnt_sph);

@@ -2913,10 +2913,40 @@ __global__ __launch_bounds__(256) void iqpt_bin_kernel(const kbin b) {
 // Round 4: also the converse per pixel, certain misses — the pixel's own bundle culls every candidate triangle
 // and sphere of its tile (iq_interval.h tri_culled / sphere_culled, the tests the tile masks are built with), so
 // every camera ray of the pixel misses everything and ends on the sky gradient (path_tracer.cu:307-316) —
-// into certain[2 ntiles + 2 t], certain[2 ntiles + 2 t + 1] (iqpt_sky_kernel's pixels).
+// into certain[2 ntiles + 2 t], certain[2 ntiles + 2 t + 1] (iqpt_sky_kernel's pixels). `certain` holds 8 ntiles
+// words: two more planes follow (round 12, below).
 // Tiles with more candidate pairs than this are left uncertain (both masks 0: traced as usual): a pixel's
 // proofs test up to every candidate, and streamed scenes (round 5) can have thousands per tile (C5's mesh).
 constexpr uint32_t kCertainMaxPairs = 96;
+// Round 12: certain hits beside a sphere — pixels of a tile WITH sphere candidates. The tile's cull is loose (a
+// tile's bundle culls a small sphere only about sqrt(2 x the tile's width) away from it), so a
+// wide ring of tiles around a sphere keeps it as a candidate although most of their pixels cannot reach it. Such
+// a pixel is a certain hit when its tile has at most kCertainMaxPairs candidate pairs, its own bundle is ok,
+// sphere_culled holds on its own bundle for every sphere of the tile's sphere candidate pairs, and some candidate
+// triangle of the tile is tri_certain on its own bundle. Soundness, by the composition the miss proof uses: a
+// sphere that is no candidate of the tile is culled for the tile's bundle, which contains the pixel's, so it
+// rejects every camera ray of the pixel; a candidate sphere culled for the pixel's own bundle rejects them too;
+// so no sphere is hit, the closest hit is a triangle (one accepts every ray), emissive under the reference's
+// materials, and the two draws and the (1, 1, 1) fold are those of the tile rule above.
+// Planes of `certain` (2 ntiles words each): [0] the hit mask by the tile rule, [1] the miss mask — both as
+// before round 12 — [2] the beside-a-sphere hit mask (only the pixels this rule adds: the proof), [3] the folded
+// mask: what kparams::certain, the queue cost and iqpt_debug_certain_tiles read. The miss mask is disjoint from
+// both hit masks. IQPT_CERTAIN_BESIDE_SPHERE=0 (A/B): plane [2] is 0 and [3] equals [0].
+// Which proven pixels fold: [3] = [0] | [2] for the tiles with at least kCertainBesideMin pixels in [2] (or all of
+// a smaller ragged tile), [0] for the others. A pixel that folds costs its wave a pass of the refill's fold (the
+// skip-ahead and the launch's samples, whatever the number of lanes folding) and saves its own lane's iterations;
+// in a tile with few proven pixels that pass falls to the wave that then carries the tile's sphere pixels, the
+// launch's longest chains, whose iterations the proven pixels shared for nothing. Measured on C2 (DESIGN.md §6
+// round 12, 100-step bench, ms per step): none 0.597-0.599, every proven pixel (1) 0.602, 8: 0.581, 16 to 48:
+// 0.574-0.578, whole tiles only (64): 0.583. Half a tile is the middle of the flat range.
+#ifndef IQPT_CERTAIN_BESIDE_SPHERE
+#define IQPT_CERTAIN_BESIDE_SPHERE 1
+#endif
+constexpr bool kCertainBesideSphere = IQPT_CERTAIN_BESIDE_SPHERE != 0;
+#ifndef IQPT_CERTAIN_BESIDE_MIN
+#define IQPT_CERTAIN_BESIDE_MIN 32
+#endif
+constexpr uint32_t kCertainBesideMin = IQPT_CERTAIN_BESIDE_MIN;
 
 __global__ __launch_bounds__(64) void iqpt_certain_kernel(const kbin b, uint32_t* certain) {
     const uint32_t t = blockIdx.x, lane = threadIdx.x;
@@ -2931,7 +2961,7 @@ __global__ __launch_bounds__(64) void iqpt_certain_kernel(const kbin b, uint32_t
     const bool small = ncand <= kCertainMaxPairs;
     const uint32_t tx = t % b.ntx, ty = t / b.ntx;
     const uint32_t tw = min(kCullTile, b.ncols - tx * kCullTile), th = min(kCullTile, b.nrows - ty * kCullTile);
-    bool ok = false, miss = false;
+    bool ok = false, miss = false, beside = false;
     if (lane < tw * th && small) {
         const uint32_t col = tx * kCullTile + lane % tw, row = ty * kCullTile + lane / tw;
         iqiv::camera_in ci;
@@ -2946,8 +2976,29 @@ __global__ __launch_bounds__(64) void iqpt_certain_kernel(const kbin b, uint32_t
         ci.far_rw = b.cam_far_rw;
         const uint32_t x = b.x0 + col, y = b.y0 + row * b.ystep;
         const iqiv::bundle bd = iqiv::camera_bundle(ci, x, x, y, y);
-        // certain hit: no sphere candidate in the tile, some candidate triangle accepts every ray
-        for (uint32_t w = 0; !sph && w < b.wt && bd.ok && !ok; ++w) {
+        // beside a sphere: the spheres first (a few at most, and most pixels near a silhouette stop here) — every
+        // sphere of the tile's sphere candidate pairs culled for the pixel's own bundle
+        bool reach = sph;                                  // some sphere may be hit by a camera ray of the pixel
+        if (kCertainBesideSphere && sph && bd.ok) {
+            reach = false;
+            for (uint32_t w = b.wt; w < b.stride && !reach; ++w) {
+                uint32_t bits = m[w];
+                while (bits && !reach) {
+                    const uint32_t j = (w - b.wt) * 32u + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1u;
+                    for (uint32_t e = 0; e < 2u && !reach; ++e) {
+                        const uint32_t k = 2u * j + e;
+                        if (k >= b.nsph) break;
+                        const float4_storage sp = b.spheres[k];
+                        const float c[3] = {sp.x, sp.y, sp.z};
+                        reach = !iqiv::sphere_culled(bd, c, sp.w);
+                    }
+                }
+            }
+        }
+        // certain hit: no sphere candidate in the tile (or none the pixel can reach), some candidate triangle
+        // accepts every ray
+        for (uint32_t w = 0; !reach && w < b.wt && bd.ok && !ok; ++w) {
             uint32_t bits = m[w];
             while (bits && !ok) {
                 const uint32_t j = w * 32u + (uint32_t)__builtin_ctz(bits);
@@ -2963,8 +3014,13 @@ __global__ __launch_bounds__(64) void iqpt_certain_kernel(const kbin b, uint32_t
                 }
             }
         }
-        // certain miss: every candidate triangle and sphere of the tile culled for the pixel's own bundle
-        miss = bd.ok && !ok;
+        if (sph) {                                         // the tile rule's plane holds tiles without a sphere only
+            beside = ok;
+            ok = false;
+        }
+        // certain miss: every candidate triangle and sphere of the tile culled for the pixel's own bundle (never
+        // a hit of either rule: a tri_certain triangle is not culled)
+        miss = bd.ok && !ok && !beside;
         for (uint32_t w = 0; w < b.stride && miss; ++w) {
             uint32_t bits = m[w];
             while (bits && miss) {
@@ -2989,13 +3045,18 @@ __global__ __launch_bounds__(64) void iqpt_certain_kernel(const kbin b, uint32_t
             }
         }
     }
-    const uint64_t mask = __ballot(ok), miss_mask = __ballot(miss);
+    const uint64_t mask = __ballot(ok), miss_mask = __ballot(miss), beside_mask = __ballot(beside);
     if (lane == 0) {
         const size_t nt = (size_t)b.ntx * b.nty;
         certain[2 * (size_t)t] = (uint32_t)mask;
         certain[2 * (size_t)t + 1] = (uint32_t)(mask >> 32);
         certain[2 * nt + 2 * (size_t)t] = (uint32_t)miss_mask;
         certain[2 * nt + 2 * (size_t)t + 1] = (uint32_t)(miss_mask >> 32);
+        certain[4 * nt + 2 * (size_t)t] = (uint32_t)beside_mask;
+        certain[4 * nt + 2 * (size_t)t + 1] = (uint32_t)(beside_mask >> 32);
+        const uint64_t fold = (uint32_t)__popcll(beside_mask) >= min(kCertainBesideMin, tw * th) ? beside_mask : 0ull;
+        certain[6 * nt + 2 * (size_t)t] = (uint32_t)(mask | fold);
+        certain[6 * nt + 2 * (size_t)t + 1] = (uint32_t)((mask | fold) >> 32);
     }
 }
 

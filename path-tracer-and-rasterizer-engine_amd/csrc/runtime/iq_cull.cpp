@@ -229,14 +229,15 @@ int build_cull(iqpt_ctx* c) {
     // (resident scenes: streamed ones with certain pixels and the sky kernel — their BVH-primary variants, which
     // have no LDS batches — measured slower on C4 in round 5, 135 -> 161 ms)
     if (!c->d_mats && ntiles > 0 && resident_bytes <= iqpt::kLdsResidentBytes) {
-        // per tile: the certain-hit mask (2 words), then after all tiles the certain-miss masks (2 words each)
-        if (hipMalloc(&c->d_certain, 4 * (size_t)ntiles * sizeof(uint32_t)) != hipSuccess)
+        // per tile: the certain-hit mask by the tile rule (2 words), then after all tiles the certain-miss masks,
+        // the beside-a-sphere hit masks and the folded hit masks (2 words each: iqpt::kCertainPlanes planes)
+        const size_t ncw = 2 * (size_t)iqpt::kCertainPlanes * ntiles;
+        if (hipMalloc(&c->d_certain, ncw * sizeof(uint32_t)) != hipSuccess)
             return iqpt::fail(IQPT_ERR_OUT_OF_MEMORY, "certain pixel masks");
         const int lc = iqpt::launch_certain(c->stream, b, c->d_certain);
         if (lc != 0) return iqpt::hip_fail((hipError_t)lc, "certain pixel kernel");
-        certain.resize(4 * (size_t)ntiles);
-        IQPT_HIP(hipMemcpyAsync(certain.data(), c->d_certain, 4 * (size_t)ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                c->stream));
+        certain.resize(ncw);
+        IQPT_HIP(hipMemcpyAsync(certain.data(), c->d_certain, ncw * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         IQPT_HIP(hipStreamSynchronize(c->stream));
         c->certain_valid = true;
         // the tiles holding certain-miss pixels: iqpt_sky_kernel's work list (one wave each)
@@ -272,8 +273,9 @@ int build_cull(iqpt_ctx* c) {
             const uint32_t tx = t % c->cull_ntx, ty = t / c->cull_ntx;
             const uint32_t npt = std::min(iqpt::kCullTile, c->ncols - tx * iqpt::kCullTile) *
                                  std::min(iqpt::kCullTile, c->set.nrows - ty * iqpt::kCullTile);
-            uint32_t nc = (uint32_t)__builtin_popcountll((uint64_t)certain[2 * (size_t)t] |
-                                                         ((uint64_t)certain[2 * (size_t)t + 1] << 32));
+            // (the folded hit mask: what the kernels fold)
+            const uint32_t* hit = certain.data() + 2 * (size_t)iqpt::kCertainFolded * ntiles;
+            uint32_t nc = (uint32_t)__builtin_popcountll((uint64_t)hit[2 * (size_t)t] | ((uint64_t)hit[2 * (size_t)t + 1] << 32));
             // certain misses leave the plain kernel's work too when the sky kernel takes them
             if (c->sky_on)
                 nc += (uint32_t)__builtin_popcountll((uint64_t)certain[2 * (size_t)ntiles + 2 * (size_t)t] |

@@ -167,7 +167,9 @@ int iqpt_debug_certain_tiles(iqpt_ctx* c, uint32_t* n, uint32_t* ntiles, uint32_
     if (!c->certain_valid || !c->d_certain) return IQPT_OK;
     const uint32_t nt = c->cull_ntx * c->cull_nty;
     std::vector<uint32_t> v(2 * (size_t)nt);
-    IQPT_HIP(hipMemcpy(v.data(), c->d_certain, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // the folded hit masks: what the kernels fold (the tile rule's pixels and the beside-a-sphere ones)
+    IQPT_HIP(hipMemcpy(v.data(), c->d_certain + 2 * (size_t)iqpt::kCertainFolded * nt, v.size() * sizeof(uint32_t),
+                       hipMemcpyDeviceToHost));
     for (size_t i = 0; i < v.size(); ++i) *n += (uint32_t)__builtin_popcount(v[i]);
     *ntiles = nt;
     if (masks) std::memcpy(masks, v.data(), std::min<size_t>(v.size(), 2 * (size_t)cap) * sizeof(uint32_t));
@@ -429,7 +431,10 @@ int iqpt_debug_certain_tile(const iqpt_camera* cam, uint32_t xa, uint32_t xb, ui
  *   4  d_pmask: the per-tile word offsets (ntiles + 1), the per-pixel mask words, then iqpt_pixel_mask_kernel's
  *      2 ntiles certain words
  *   5  d_tris: ntri x 12 floats (v0, e1, e2 world space, three pad words)
- *   6  d_sph: nsph x 4 floats (centre, radius) */
+ *   6  d_sph: nsph x 4 floats (centre, radius)
+ *   7  d_certain's third plane: 2 ntiles words of beside-a-sphere hit masks (the pixels of tiles with a sphere
+ *      candidate that iqpt_certain_kernel proves certain hits; the folded masks kparams::certain reads are the
+ *      hit masks of 2 OR these, iqpt_debug_certain_tiles) */
 int iqpt_debug_read_proofs(iqpt_ctx* c, int what, uint32_t* out, uint64_t cap, uint64_t* n) {
     if (!c || !n) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
     *n = 0;
@@ -454,6 +459,7 @@ int iqpt_debug_read_proofs(iqpt_ctx* c, int what, uint32_t* out, uint64_t cap, u
     case 4: if (pm) { src = c->d_pmask; words = nt + 1 + c->pmask_words + 2 * nt; } break;
     case 5: if (c->d_tris) { src = c->d_tris; words = (uint64_t)c->ntri * iqpt::kTriFloat4 * 4; } break;
     case 6: if (c->d_sph) { src = c->d_sph; words = (uint64_t)c->nsph * 4; } break;
+    case 7: if (grid[6]) { src = c->d_certain + 2 * iqpt::kCertainBeside * nt; words = 2 * nt; } break;
     default: return iqpt::fail(IQPT_ERR_INVALID_ARG, "unknown buffer selector");
     }
     *n = words;

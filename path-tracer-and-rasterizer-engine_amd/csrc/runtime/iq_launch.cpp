@@ -173,7 +173,10 @@ void fill_scene_params(const iqpt_ctx* c, uint32_t spp, iqpt::kparams& p) {
 // ... and the tile masks, candidate lists and per-pixel masks of the current camera and packet (build_cull)
 void fill_mask_params(const iqpt_ctx* c, iqpt::kparams& p) {
     p.cull = c->d_cull;
-    p.certain = c->certain_valid && c->certain_on ? c->d_certain : nullptr;
+    // (the folded hit masks of iqpt_certain_kernel's planes: the tile rule's and the beside-a-sphere pixels)
+    p.certain = c->certain_valid && c->certain_on
+                    ? c->d_certain + 2 * (size_t)iqpt::kCertainFolded * c->cull_ntx * c->cull_nty
+                    : nullptr;
     p.tile_order = c->d_tile_order;
     p.cull_ntx = c->cull_ntx;
     p.cull_wt = c->cull_wt;

@@ -312,6 +312,18 @@ def build_sky_libs(force: bool = False) -> list[Path]:
     return [build_lib(force, flags=SKY_SINGLE_FLAGS, target=SKY_SINGLE_LIB)]
 
 
+# iqpt_certain_kernel without the beside-a-sphere rule (the folded hit masks equal the tile rule's: the form before
+# it): an A/B library for bench.py --lib and the tools' --lib, and the other side of
+# tests/test_gpu_certain_beside_sphere.py.
+CERTAIN_TILE_RULE_FLAGS = ("-DIQPT_CERTAIN_BESIDE_SPHERE=0",)
+CERTAIN_TILE_RULE_LIB = PKG_DIR / "libiqpt_certaintile.so"
+
+
+def build_certain_libs(force: bool = False) -> list[Path]:
+    """The library tests/test_gpu_certain_beside_sphere.py compares the default one with (measurement and test only)."""
+    return [build_lib(force, flags=CERTAIN_TILE_RULE_FLAGS, target=CERTAIN_TILE_RULE_LIB)]
+
+
 def kernel_resources(target: Path = LIB_PATH, stats: bool = False) -> dict[str, dict[str, int]]:
     """Per kernel of iqpt_kernels.hip as compiled into `target` (a library build_lib has built): the compiler's
     resource remarks (-Rpass-analysis=kernel-resource-usage, kept beside the object), as
@@ -353,8 +365,9 @@ def build_all(force: bool = False) -> None:
     build_tools(force)
     build_oracle(force)
     build_ref(force)
-    with ThreadPoolExecutor(max_workers=3) as ex:
-        list(ex.map(lambda f: f(force), (build_pair_body_libs, build_scatter_libs, build_sky_libs)))
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        list(ex.map(lambda f: f(force), (build_pair_body_libs, build_scatter_libs, build_sky_libs,
+                                         build_certain_libs)))
 
 
 if __name__ == "__main__":

@@ -470,5 +470,11 @@ void bind_launch_events(void* start, void* stop);
 constexpr int kRenderBlock = 256;
 constexpr uint32_t kQueueChunk = 64;
 const char* render_kernel_name();
+// The variant tables of iqpt_kernels.hip as data (iqpt_debug_variant_table, iqpt_debug_last_launch): a table's
+// row as (maxd, streamed, opt) with -1 for a field it does not have (false past its end), and the row its
+// launcher takes for a launch (-1: none). Hidden: the library's use only, not in its dynamic symbol table.
+enum { kTableRender = 0, kTableFan = 1, kTableSky = 2, kTableAnyHit = 3, kTableSpec = 4, kTableStitch = 5 };
+__attribute__((visibility("hidden"))) bool variant_table_row(int table, uint32_t row, int out3[3]);
+__attribute__((visibility("hidden"))) int variant_row(int table, int max_depth, bool stream_batches, int opt);
 
 }  // namespace iqpt

@@ -4674,14 +4674,19 @@ int launch_split_prep(void* stream, const ksplit& s) {
     return (int)hipGetLastError();
 }
 
+// iqpt_split_stitch_kernel's two forms: row 0 with the running mean's short division, row 1 with the generic one
+namespace {
+constexpr int kStitchVariants[] = {kOptDefault, kOptDefault & ~kOptFastDiv};
+}  // namespace
+
 int launch_split_stitch(void* stream, const ksplit& s, bool fastdiv) {
     if (s.ns_cap == 0) return 0;
     if (s.spp > kAccTableMax) return (int)hipErrorInvalidValue;
     const dim3 grid((s.ns_cap + kStitchBlock - 1) / kStitchBlock);
     if (fastdiv)
-        hipLaunchKernelGGL(iqpt_split_stitch_kernel<kOptDefault>, grid, dim3(kStitchBlock), 0, (hipStream_t)stream, s);
+        hipLaunchKernelGGL(iqpt_split_stitch_kernel<kStitchVariants[0]>, grid, dim3(kStitchBlock), 0, (hipStream_t)stream, s);
     else
-        hipLaunchKernelGGL(iqpt_split_stitch_kernel<(kOptDefault & ~kOptFastDiv)>, grid, dim3(kStitchBlock), 0,
+        hipLaunchKernelGGL(iqpt_split_stitch_kernel<kStitchVariants[1]>, grid, dim3(kStitchBlock), 0,
                            (hipStream_t)stream, s);
     return (int)hipGetLastError();
 }
@@ -4696,14 +4701,17 @@ int fan_launch_t(hipStream_t stream, const kparams& p, uint32_t grid, uint32_t l
 }
 struct fan_variant {
     int key;
+    int opt;    // the instantiated option set (variant_table)
     int (*launch)(hipStream_t, const kparams&, uint32_t, uint32_t);
 };
 constexpr int kFanKeyBits = kOptFastDiv | kOptCamAxis;
+#define IQPT_FV(O) {(O) & kFanKeyBits, O, fan_launch_t<O>}
 const fan_variant kFanVariants[] = {
-    {kOptFastDiv, fan_launch_t<kOptDefault>},
-    {0, fan_launch_t<kOptDefault & ~kOptFastDiv>},
-    {kOptFastDiv | kOptCamAxis, fan_launch_t<kOptDefault | kOptCamAxis>},
+    IQPT_FV(kOptDefault),
+    IQPT_FV(kOptDefault & ~kOptFastDiv),
+    IQPT_FV(kOptDefault | kOptCamAxis),
 };
+#undef IQPT_FV
 const fan_variant* find_fan(int opt) {
     // the production option sets differ from kOptDefault only in these bits (and in bits the fan
     // kernel does not read: priority, overlap, split)
@@ -4728,13 +4736,16 @@ int sky_launch_t(hipStream_t stream, const kparams& p, const uint32_t* tiles, ui
 }
 struct sky_variant {
     int key;
+    int opt;
     int (*launch)(hipStream_t, const kparams&, const uint32_t*, uint32_t, uint32_t);
 };
+#define IQPT_KV(O) {(O) & kFanKeyBits, O, sky_launch_t<O>}
 const sky_variant kSkyVariants[] = {
-    {kOptFastDiv, sky_launch_t<kOptDefault>},
-    {0, sky_launch_t<kOptDefault & ~kOptFastDiv>},
-    {kOptFastDiv | kOptCamAxis, sky_launch_t<kOptDefault | kOptCamAxis>},
+    IQPT_KV(kOptDefault),
+    IQPT_KV(kOptDefault & ~kOptFastDiv),
+    IQPT_KV(kOptDefault | kOptCamAxis),
 };
+#undef IQPT_KV
 const sky_variant* find_sky(int opt) {
     // (kOptStats launches keep the sky kernel: it runs no intersection test, and the instrumented plain kernel
     // beside it then counts the tests of the pixels it renders in production, tools/work_counters.py)
@@ -4765,13 +4776,17 @@ int anyhit_launch_t(hipStream_t stream, const kparams& p, uint32_t lds) {
 }
 struct anyhit_variant {
     int key;
+    int opt;
     int (*launch)(hipStream_t, const kparams&, uint32_t);
 };
+#define IQPT_AV(O) {(O) & kFanKeyBits, O, anyhit_launch_t<O>}
 const anyhit_variant kAnyVariants[] = {
-    {kOptFastDiv, anyhit_launch_t<kOptDefault>},
-    {0, anyhit_launch_t<kOptDefault & ~kOptFastDiv>},
-    {kOptFastDiv | kOptCamAxis, anyhit_launch_t<kOptDefault | kOptCamAxis>},
+    IQPT_AV(kOptDefault),
+    IQPT_AV(kOptDefault & ~kOptFastDiv),
+    // (no kOptCamAxis row: the kernel runs for streamed scenes only, and the runtime adds that bit to resident
+    // launches only; a caller's fixed option set never reaches this kernel)
 };
+#undef IQPT_AV
 const anyhit_variant* find_anyhit(int opt) {
     if ((opt & (kOptAccTable | kOptCamConst | kOptPair)) != (kOptAccTable | kOptCamConst | kOptPair) ||
         (opt & (kOptMaterials | kOptStats)))
@@ -4856,6 +4871,61 @@ int spec_occupancy(const kparams& p, const kspec& s, int opt, int* blocks) {
     const spec_variant* v = find_spec(p.max_depth, opt);
     if (!v) return (int)hipErrorInvalidDeviceFunction;
     return v->occ(spec_lds(p, s), blocks);
+}
+
+// The tables above as data (iqpt_debug_variant_table): row `row` of table `table` (kTable*) as (maxd, streamed,
+// opt), -1 for a field the table does not have; false past the table's end. Fan, sky and any-hit rows give the
+// instantiated option set, not the key.
+bool variant_table_row(int table, uint32_t row, int out3[3]) {
+    out3[0] = out3[1] = out3[2] = -1;
+    switch (table) {
+    case kTableRender:
+        if (row >= sizeof kVariants / sizeof kVariants[0]) return false;
+        out3[0] = kVariants[row].maxd;
+        out3[1] = kVariants[row].stream ? 1 : 0;
+        out3[2] = kVariants[row].opt;
+        return true;
+    case kTableFan:
+        if (row >= sizeof kFanVariants / sizeof kFanVariants[0]) return false;
+        out3[2] = kFanVariants[row].opt;
+        return true;
+    case kTableSky:
+        if (row >= sizeof kSkyVariants / sizeof kSkyVariants[0]) return false;
+        out3[2] = kSkyVariants[row].opt;
+        return true;
+    case kTableAnyHit:
+        if (row >= sizeof kAnyVariants / sizeof kAnyVariants[0]) return false;
+        out3[2] = kAnyVariants[row].opt;
+        return true;
+    case kTableSpec:
+        if (row >= sizeof kSpecVariants / sizeof kSpecVariants[0]) return false;
+        out3[0] = kSpecVariants[row].maxd;
+        out3[1] = 0;
+        out3[2] = kSpecVariants[row].opt;
+        return true;
+    case kTableStitch:
+        if (row >= sizeof kStitchVariants / sizeof kStitchVariants[0]) return false;
+        out3[2] = kStitchVariants[row];
+        return true;
+    default: return false;
+    }
+}
+
+// The row the launchers above take for (max_depth, stream_batches, opt), by the same lookups (launch_render,
+// launch_fan, launch_sky, launch_anyhit, launch_spec; launch_split_stitch reads kOptFastDiv of opt); -1: none.
+int variant_row(int table, int max_depth, bool stream_batches, int opt) {
+    switch (table) {
+    case kTableRender: { const variant* v = find_variant(max_depth, stream_batches, opt); return v ? (int)(v - kVariants) : -1; }
+    case kTableFan: { const fan_variant* v = find_fan(opt); return v ? (int)(v - kFanVariants) : -1; }
+    case kTableSky: { const sky_variant* v = find_sky(opt); return v ? (int)(v - kSkyVariants) : -1; }
+    case kTableAnyHit: { const anyhit_variant* v = find_anyhit(opt); return v ? (int)(v - kAnyVariants) : -1; }
+    case kTableSpec: {
+        const spec_variant* v = max_depth <= 16 ? find_spec(max_depth, opt) : nullptr;
+        return v ? (int)(v - kSpecVariants) : -1;
+    }
+    case kTableStitch: return (opt & kOptFastDiv) ? 0 : 1;
+    default: return -1;
+    }
 }
 
 }  // namespace iqpt

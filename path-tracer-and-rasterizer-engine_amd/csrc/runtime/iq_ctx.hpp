@@ -135,6 +135,11 @@ struct iqpt_ctx {
     bool tune_primary = false;
     hipEvent_t tune_ev[2 * 4] = {};
     int last_opt = -1;           // option set of the last render launch (iqpt_debug_last_options)
+    // the kernels of the last render launch (iqpt_debug_last_launch): maxd, streamed, the plain or spec kernel's
+    // option set, then the rows of the sky, fan, spec, any-hit and split-stitch tables it launched (-1: not
+    // launched). cur_launch is the launch being enqueued (note_kernel); it becomes last_launch where last_opt is set
+    int32_t last_launch[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    int32_t cur_launch[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     bool last_xcd_lists = false; // the last launch dealt its tiles to per-XCD lists (overlapped or streamed)
     // kOptSplit, sample-parallel chains: mode (IQPT_SPLIT_*), the split set built with
     // the masks (tiles whose camera rays may scatter), per-slot buffers sized for the launch

@@ -638,6 +638,36 @@ int iqpt_debug_last_options(iqpt_ctx* c, int* opt) {
     return IQPT_OK;
 }
 
+/* Internal (tests/test_variant_cases.py, tests/test_gpu_variant_census.py): the kernel variant tables of
+ * iqpt_kernels.hip as data, three int32 per row: maxd (8 or 16), streamed (0 or 1), opt (the instantiated kOpt* set);
+ * -1 for a field the table does not have. table: 0 iqpt_render_kernel, 1 iqpt_fan_kernel, 2 iqpt_sky_kernel,
+ * 3 iqpt_anyhit_kernel, 4 iqpt_spec_kernel, 5 iqpt_split_stitch_kernel. *nrows = the table's rows; up to cap_rows of
+ * them are written to out (which may be NULL with cap_rows 0). Reads the arrays the launchers search. Host only: no
+ * context, no device. */
+int iqpt_debug_variant_table(int table, int32_t* out, uint32_t cap_rows, uint32_t* nrows) {
+    if (!nrows || (cap_rows && !out)) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    *nrows = 0;
+    if (table < iqpt::kTableRender || table > iqpt::kTableStitch) return iqpt::fail(IQPT_ERR_INVALID_ARG, "table not 0..5");
+    int r3[3];
+    uint32_t n = 0;
+    for (; iqpt::variant_table_row(table, n, r3); ++n)
+        if (n < cap_rows)
+            for (int k = 0; k < 3; ++k) out[3 * (size_t)n + k] = r3[k];
+    *nrows = n;
+    return IQPT_OK;
+}
+
+/* Internal (tests/test_gpu_variant_census.py): the kernels of the context's last render launch (of the last launch
+ * of an iqpt_render call that the running-mean table splits in several). out8: 0 maxd, 1 streamed, 2 the option set of
+ * the plain kernel (iqpt_debug_last_options without its bits 29 and 30) or of the spec kernel's row, -1 if neither
+ * ran; 3..7 the rows of iqpt_debug_variant_table's tables 2 (sky), 1 (fan), 4 (spec), 3 (any-hit) and 5 (split-stitch)
+ * the launch ran, -1 for a kernel it did not launch. All -1 before the first launch. */
+int iqpt_debug_last_launch(iqpt_ctx* c, int32_t* out8) {
+    if (!c || !out8) return iqpt::fail(IQPT_ERR_INVALID_ARG, "NULL argument");
+    std::memcpy(out8, c->last_launch, sizeof c->last_launch);
+    return IQPT_OK;
+}
+
 /* Internal (tools/wave_timeline.py): per wave slot of the last kOptStats launch, the shader-clock cycles spent in the
  * closest hits, the shading, the next rays and the rest of the loop (kStatsPhaseWords each, same slots as
  * iqpt_debug_read_wave_times). Call before iqpt_debug_read_stats. */

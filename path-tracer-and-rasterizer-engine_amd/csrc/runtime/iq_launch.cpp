@@ -526,6 +526,26 @@ int spec_history(iqpt_ctx* c, hipStream_t ss, const iqpt::kspec& ks2) {
     return IQPT_OK;
 }
 
+// ---- iqpt_debug_last_launch's bookkeeping, beside each kernel's enqueue: the plain kernel's option set, and the
+// row of its table an auxiliary kernel's launcher takes for `opt` (iqpt::variant_row, the launchers' own lookups)
+void note_plain(iqpt_ctx* c, int opt) { c->cur_launch[2] = opt; }
+void note_kernel(iqpt_ctx* c, int table, int opt) {
+    const int row = iqpt::variant_row(table, c->max_depth, false, opt);
+    switch (table) {
+    case iqpt::kTableSky: c->cur_launch[3] = row; break;
+    case iqpt::kTableFan: c->cur_launch[4] = row; break;
+    case iqpt::kTableSpec: {
+        int r3[3];
+        c->cur_launch[5] = row;
+        c->cur_launch[2] = row >= 0 && iqpt::variant_table_row(table, (uint32_t)row, r3) ? r3[2] : -1;
+        break;
+    }
+    case iqpt::kTableAnyHit: c->cur_launch[6] = row; break;
+    case iqpt::kTableStitch: c->cur_launch[7] = row; break;
+    default: break;
+    }
+}
+
 // ---- the enqueue of overlapped, spec and split launches; le: the kernels' launch status (reported after the
 // bookkeeping). Overlapped: the plain kernel on ls, the sky kernel behind it where it was deferred
 int enqueue_overlapped(iqpt_ctx* c, const iqpt::kparams& p, hipStream_t ls, uint32_t grid, uint32_t lds, int opt,
@@ -533,6 +553,7 @@ int enqueue_overlapped(iqpt_ctx* c, const iqpt::kparams& p, hipStream_t ls, uint
                        bool& e1_bound, int& le) {
     if (bind_ovl) iqpt::bind_launch_events(e0_bound ? nullptr : e0, sky_deferred ? nullptr : e1);
     le = iqpt::launch_render(ls, p, grid, lds, false, opt);
+    note_plain(c, opt);
     iqpt::bind_launch_events(nullptr, nullptr);
     if (bind_ovl) {
         if (le != 0 && e0 && !e0_bound) (void)hipEventRecord(e0, ls);   // (not read: the launch failed)
@@ -543,6 +564,7 @@ int enqueue_overlapped(iqpt_ctx* c, const iqpt::kparams& p, hipStream_t ls, uint
         if (c->sky_last && c->sky_last != ls) IQPT_HIP(hipStreamWaitEvent(ls, c->ev_sky, 0));
         iqpt::bind_launch_events(nullptr, e1);
         le = iqpt::launch_sky(ls, p, c->d_sky_tiles, c->n_sky_tiles, opt);
+        note_kernel(c, iqpt::kTableSky, opt);
         iqpt::bind_launch_events(nullptr, nullptr);
         e1_bound = le == 0 && e1 != nullptr;
         if (le != 0) return iqpt::hip_fail((hipError_t)le, "sky kernel launch");
@@ -573,11 +595,16 @@ int enqueue_spec(iqpt_ctx* c, iqpt::kparams& p, uint32_t spp, int opt, bool pipe
         iqpt::kparams pm = pf;
         pm.miss = c->d_certain + 2 * (size_t)c->cull_ntx * c->cull_nty;
         le = iqpt::launch_sky(c->specfan_mode == 0 ? c->stream2 : c->stream, pm, c->d_sky_tiles, c->n_sky_tiles, opt);
+        if (c->n_sky_tiles > 0) note_kernel(c, iqpt::kTableSky, opt);
         if (le != 0) return iqpt::hip_fail((hipError_t)le, "sky kernel launch");
     }
     if ((st = spec_plan(c, p, opt, c->stream, ks2)) != IQPT_OK) return st;
     const uint32_t n = ks2.n;
-    auto run_spec = [&]() -> int { return iqpt::launch_spec(c->stream, p, ks2, opt); };
+    auto run_spec = [&]() -> int {
+        note_kernel(c, iqpt::kTableSpec, opt);
+        return iqpt::launch_spec(c->stream, p, ks2, opt);
+    };
+    if (le == 0 && c->n_fan_tiles > 0) note_kernel(c, iqpt::kTableFan, opt);   // (either branch launches it)
     if (c->specfan_mode == 1) {
         if (n > 0) le = run_spec();
         if (le == 0 && c->n_fan_tiles > 0) le = iqpt::launch_fan(c->stream, pf, c->n_fan_tiles, opt);
@@ -616,13 +643,16 @@ int enqueue_split(iqpt_ctx* c, iqpt::kparams& p, const iqpt::ksplit& ks, uint32_
         IQPT_HIP(hipEventRecord(c->ev_pre, c->stream));
         IQPT_HIP(hipStreamWaitEvent(c->stream2, c->ev_pre, 0));
         le = iqpt::launch_fan(c->stream2, pf, c->n_anchor, opt);
+        if (c->n_anchor > 0) note_kernel(c, iqpt::kTableFan, opt);
         p.n_anchor = 0;
     }
     if (le == 0) le = iqpt::launch_split_prep(c->stream, ks);
     p.split_round = 1;
     p.queue = c->d_queue;
     if (le == 0) le = iqpt::launch_render(c->stream, p, grid, lds, false, opt);
+    note_plain(c, opt);
     if (le == 0) le = iqpt::launch_split_stitch(c->stream, ks, (opt & iqpt::kOptFastDiv) != 0);
+    if (ks.ns_cap > 0) note_kernel(c, iqpt::kTableStitch, opt);
     p.split_round = 2;
     p.queue = c->d_queue + 1;
     if (le == 0) le = iqpt::launch_render(c->stream, p, grid, lds, false, opt);
@@ -850,6 +880,9 @@ int render_launch(iqpt_ctx* c, uint32_t spp) {
     if (e0 && !bind_spec && !bind_ovl) (void)hipEventRecord(e0, ls);
     if (tune_slot >= 0) (void)hipEventRecord(c->tune_ev[2 * tune_slot], c->stream);
     int le = 0;
+    for (int32_t& v : c->cur_launch) v = -1;
+    c->cur_launch[0] = c->max_depth <= 8 ? 8 : 16;
+    c->cur_launch[1] = stream_batches ? 1 : 0;
     // certain-miss pixels: plain launches hand them to iqpt_sky_kernel, ahead of the plain
     // kernel on the launch's stream; the plain kernel skips them. Consecutive sky kernels order themselves
     // through ev_sky (overlapped launches alternate streams); their pixels are disjoint from the plain kernel's.
@@ -872,6 +905,7 @@ int render_launch(iqpt_ctx* c, uint32_t spp) {
             const bool b0 = bind_ovl && e0 && p.spp > 0;
             if (b0) iqpt::bind_launch_events(e0, nullptr);
             le = iqpt::launch_sky(ss, p, c->d_sky_tiles, c->n_sky_tiles, opt);
+            note_kernel(c, iqpt::kTableSky, opt);
             iqpt::bind_launch_events(nullptr, nullptr);
             e0_bound = b0 && le == 0;
             if (le != 0) return iqpt::hip_fail((hipError_t)le, "sky kernel launch");
@@ -888,8 +922,10 @@ int render_launch(iqpt_ctx* c, uint32_t spp) {
         if ((st = enqueue_split(c, p, ks, grid, lds, opt, fan_split, le)) != IQPT_OK) return st;
     } else if (anyk) {
         le = iqpt::launch_anyhit(c->stream, p, opt);
+        note_kernel(c, iqpt::kTableAnyHit, opt);
     } else {
         le = iqpt::launch_render(c->stream, p, grid, lds, stream_batches, opt);
+        note_plain(c, opt);
     }
     c->last_anyk = anyk;
     c->split_last = split;
@@ -903,6 +939,7 @@ int render_launch(iqpt_ctx* c, uint32_t spp) {
     if (e0 && e1) c->timed.push_back({e0, e1, e1b});
     if (le != 0) return iqpt::hip_fail((hipError_t)le, "render kernel launch");
     c->last_opt = opt;
+    std::memcpy(c->last_launch, c->cur_launch, sizeof c->last_launch);
     if (tune_slot >= 0) {
         c->tune_work[tune_slot] = (double)spp * (double)c->npix;
         c->tune_stage = tune_slot + 1;

@@ -318,6 +318,15 @@ UPSCALE_SIGNATURES = [
     ("iqpt_upscale_stats", C.c_int, [_P, _U64P, _U64P, _U64P]),
 ]
 
+# the kernel variant tables and the last launch's kernels (csrc/runtime/iq_debug.cpp; not part of include/iqpt.h):
+# the variant census of tests/variant_cases.py reads both
+VARIANT_TABLES = ("render", "fan", "sky", "anyhit", "spec", "stitch")     # iqpt_debug_variant_table's table numbers
+_I32P = C.POINTER(C.c_int32)
+DEBUG_SIGNATURES = [
+    ("iqpt_debug_variant_table", C.c_int, [C.c_int, _I32P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("iqpt_debug_last_launch", C.c_int, [_P, _I32P]),
+]
+
 _lib = None
 
 
@@ -343,7 +352,7 @@ def load() -> C.CDLL:
     if abi is not None and abi > ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI {abi}, newer than these bindings' {ABI_VERSION}")
     for name, res, args in SIGNATURES + RASTER_SIGNATURES + DENOISE_SIGNATURES + TEMPORAL_SIGNATURES + SVGF_SIGNATURES + \
-            UPSCALE_SIGNATURES:
+            UPSCALE_SIGNATURES + DEBUG_SIGNATURES:
         fn = getattr(lib, name, None)
         if fn is None:
             if own:
